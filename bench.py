@@ -19,7 +19,12 @@ under frame t+1's kernels:
 total work is fixed as N grows (`scaling: strong`); `value` = rays of the frame x steps / wall time (max over
 ranks).  Rank 0 prints ONE JSON line.  `median_ms_per_step` comes from HIP events recorded at every step boundary.
 
-`roofline`: the dominant kernel is the fp32-MFMA canonical MLP (occnerf_amd/csrc/mlp16.hip).
+A plain run sets up, warms up, times the `--steps` frames and prints the line: the headline alone.  `--full` adds everything
+described below (`roofline`, `cpu_baseline` and the side legs; `--no-alt`, `--no-cpu-baseline` and `--only` narrow it).
+`--dump-outputs DIR` writes what the last timed step returned on rank 0 -- rgb [R,3], alpha [R], depth [R] in float32 -- as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+`roofline` (--full): the dominant kernel is the fp32-MFMA canonical MLP (occnerf_amd/csrc/mlp16.hip).
 achieved = 923 136 FLOP/sample x samples per launch / average launch duration, measured
 with HIP events recorded on the launch stream around every launch inside the timed region.
 `cpu_baseline`: the CPU oracle (a port of the reference path, OpenMP on all host cores of
@@ -148,6 +153,15 @@ def timed_steps(renderer, frame_h, steps, warmup, rank, world, dev, order_key, h
         dist.barrier()
     dt = time.perf_counter() - t0
     return dt, [events[i].elapsed_time(events[i + 1]) for i in range(len(events) - 1)]
+
+
+def dump_outputs(out_dir, packed):
+    """--dump-outputs: what a caller of the timed path receives for the last timed frame (ShardedRenderer.finish: rgb [R,3],
+    alpha [R], depth [R], rays in the frame's ray_mask order) as float32 out_dir/<name>.npy; 20 B per ray, 5.2 MB at most."""
+    os.makedirs(out_dir, exist_ok=True)
+    a = packed.numpy()
+    for name, arr in (('rgb', a[:, :3]), ('alpha', a[:, 3]), ('depth', a[:, 4])):
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 # Compulsory HBM traffic of one training step of the STAGED design (one kernel per stage, intermediates in HBM), bytes per
@@ -497,17 +511,23 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--cpu-rays', type=int, default=4096, help='rays in the CPU baseline sample')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-alt', action='store_true', help='skip the side measurements (bf16x3, all samples, train)')
+    ap.add_argument('--full', action='store_true', help='also run everything beside the headline: the roofline (HIP events '
+                                                        'around every launch of the timed steps), the side legs and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the rgb / alpha / depth of the last timed step to DIR/<name>.npy (float32)')
+    ap.add_argument('--cpu-rays', type=int, default=4096, help='rays in the CPU baseline sample (--full)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-alt', action='store_true', help='--full without the side legs (bf16x3, all samples, train, ...)')
     ap.add_argument('--rccl-inline', action='store_true', help=argparse.SUPPRESS)      # (the child process of the rccl_world1 leg)
-    ap.add_argument('--only', default=None, help='comma-separated side legs to run beside the headline (default: all): '
+    ap.add_argument('--only', default=None, help='with --full: comma-separated side legs to run beside the headline (default: all): '
                                                  'dedup,rccl_world1,alt,alt2,no_shortcuts,all_samples,train,movement,freeview_orbit,config4')
     args = ap.parse_args()
+    if args.only is not None and not args.full:
+        ap.error('--only picks among the side legs, which run with --full only')
     only = None if args.only is None else set(args.only.split(','))
 
     def leg(name):
-        return not args.no_alt and (only is None or name in only)
+        return args.full and not args.no_alt and (only is None or name in only)
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:      # no launcher around us: start the ranks ourselves
         raise SystemExit(self_launch(args.gpus))
@@ -577,7 +597,8 @@ def main():
     # The headline evaluates every live sample (the definition of rounds 1-2); the renderer's default also evaluates runs of
     # bitwise identical samples once (cfg.dedup_repeated_samples, bit-identical pixels): reported beside it as `dedup`.
     net.cfg.dedup_repeated_samples = False
-    ops.canonical_mlp, ops.nonrigid_rows = timed_mlp, timed_nr
+    if args.full:                   # (a plain run times the path alone: no per-launch events, no roofline)
+        ops.canonical_mlp, ops.nonrigid_rows = timed_mlp, timed_nr
     timed_steps(renderer, frame_h, 1, args.warmup, rank, world, dev, 'bench', host_out)   # warm-up (+1 step)
     mlp_events.clear()
     nr_events.clear()
@@ -585,6 +606,8 @@ def main():
     main_events, main_nr = list(mlp_events), list(nr_events)
     ops.canonical_mlp, ops.nonrigid_rows = real_mlp, real_nr
     torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_out)
     headline_out = host_out.clone() if world == 1 else None      # rank 0's [R,5] of the last timed frame
     # balance of the shard plan: rays and live samples every rank rendered in the last frame (read after the timed region)
     my_rays, my_live = renderer.shard_stats()
@@ -632,8 +655,8 @@ def main():
                 else:
                     import subprocess
                     child = subprocess.run([sys.executable, os.path.abspath(__file__), '--gpus', '1', '--steps',
-                                            str(max(3, args.steps // 2)), '--warmup', '2', '--no-cpu-baseline', '--only', 'rccl_world1',
-                                            '--rccl-inline'], capture_output=True, text=True, timeout=400,
+                                            str(max(3, args.steps // 2)), '--warmup', '2', '--full', '--no-cpu-baseline', '--only',
+                                            'rccl_world1', '--rccl-inline'], capture_output=True, text=True, timeout=400,
                                            env={k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')})
                     lines = [l for l in child.stdout.splitlines() if l.startswith('{')]
                     if child.returncode != 0 or not lines:
@@ -765,14 +788,34 @@ def main():
                                'note': 'one whole frame per rank per step, no gather (every rank keeps its frame)'}
 
     if rank == 0:
-        ms = [e0.elapsed_time(e1) for e0, e1, _ in main_events]
-        nsmp = [int(n) for _, _, n in main_events]          # (read back after the timed region)
-        avg_ms = float(np.mean(ms))
-        achieved = FLOP_PER_SAMPLE_CNL * float(np.mean(nsmp)) / (avg_ms * 1e-3)
-        traffic, traffic_src = pmc_traffic(float(np.mean(nsmp)))
-        nr_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in main_nr])) if main_nr else None
-        live = float(np.mean(nsmp))
         step_s = dt / args.steps
+        live = roofline = None
+        if args.full:
+            ms = [e0.elapsed_time(e1) for e0, e1, _ in main_events]
+            nsmp = [int(n) for _, _, n in main_events]          # (read back after the timed region)
+            avg_ms = float(np.mean(ms))
+            live = float(np.mean(nsmp))
+            achieved = FLOP_PER_SAMPLE_CNL * live / (avg_ms * 1e-3)
+            traffic, traffic_src = pmc_traffic(live)
+            nr_ms = float(np.mean([e0.elapsed_time(e1) for e0, e1 in main_nr])) if main_nr else None
+            roofline = {'bound': 'mfma', 'kernel': 'occ::m16::canonical_mlp_lds_kernel (fp32 MFMA 16x16x4, LDS-staged weights)',
+                        'achieved': achieved / 1e12, 'peak': PEAK_FP32_MFMA / 1e12, 'unit': 'TFLOP/s',
+                        'frac': achieved / PEAK_FP32_MFMA, 'traffic': traffic,
+                        'traffic_note': f'NOT measured in this run: read from the committed file profiles/{traffic_src} (separate '
+                                        'rocprofv3 --pmc passes over this very launch size, tools/pmc_hbm.sh: HBM bytes per '
+                                        'launch = FETCH_SIZE x2 + WRITE_SIZE with the guide\'s gfx950 corrections); null when no '
+                                        'committed pass matches the launch size; algorithmic 288 B/sample',
+                        'launch_ms': avg_ms, 'launches_timed': len(ms),
+                        'flop_per_launch': FLOP_PER_SAMPLE_CNL * live,
+                        # the second MFMA kernel of the frame (rank 0's launches): algorithmic 200 704 FLOP per live sample
+                        # (91 520 MAC = 183 040 FLOP executed after folding the 69 per-frame condition inputs into a bias)
+                        'nonrigid': None if nr_ms is None else {
+                            'kernel': 'occ::nr16::nonrigid_lds_kernel', 'launch_ms': nr_ms,
+                            'achieved_algorithmic': FLOP_PER_SAMPLE_NR * live / (nr_ms * 1e-3) / 1e12,
+                            'frac_algorithmic': FLOP_PER_SAMPLE_NR * live / (nr_ms * 1e-3) / PEAK_FP32_MFMA,
+                            'frac_executed': 183040 * live / (nr_ms * 1e-3) / PEAK_FP32_MFMA},
+                        # whole step: canonical + non-rigid algorithmic FLOP of the samples rank 0 evaluated / step time
+                        'end_to_end_frac': (FLOP_PER_SAMPLE_CNL + FLOP_PER_SAMPLE_NR) * live / step_s / PEAK_FP32_MFMA}
         line = {
             'metric': 'rays/sec at 512x512x128spp, random-init ckpt', 'value': R * args.steps / dt,
             'unit': 'rays/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -786,7 +829,7 @@ def main():
                                    'motion-weight sum is exactly 0 are dropped after the warp (bit-identical pixels, see all_samples); every other '
                                    'sample is evaluated (the renderer\'s run-length elimination of identical samples is OFF here, see dedup)',
                        'rays_per_frame': R, 'samples_per_ray': SPP, 'image': [IMG, IMG],
-                       'samples_evaluated_per_launch': float(np.mean(nsmp)),
+                       **({'samples_evaluated_per_launch': live} if live is not None else {}),
                        'skip_empty_samples': bool(net.cfg.get('skip_empty_samples', True)),
                        'dedup_repeated_samples': False,
                        'knn_center_cache': bool(net.cfg.get('knn_center_cache', True)),
@@ -797,27 +840,11 @@ def main():
                        'per_rank_live_samples': [p[1] for p in per_rank],
                        'parallelism': f'one frame, its Morton walk dealt to {world} rank(s) in 256-ray blocks, async RCCL gather '
                                       'to rank 0 overlapped with the next frame'},
-            'roofline': {'bound': 'mfma', 'kernel': 'occ::m16::canonical_mlp_lds_kernel (fp32 MFMA 16x16x4, LDS-staged weights)',
-                         'achieved': achieved / 1e12, 'peak': PEAK_FP32_MFMA / 1e12, 'unit': 'TFLOP/s',
-                         'frac': achieved / PEAK_FP32_MFMA, 'traffic': traffic,
-                         'traffic_note': f'NOT measured in this run: read from the committed file profiles/{traffic_src} (separate '
-                                         'rocprofv3 --pmc passes over this very launch size, tools/pmc_hbm.sh: HBM bytes per '
-                                         'launch = FETCH_SIZE x2 + WRITE_SIZE with the guide\'s gfx950 corrections); null when no '
-                                         'committed pass matches the launch size; algorithmic 288 B/sample',
-                         'launch_ms': avg_ms, 'launches_timed': len(ms),
-                         'flop_per_launch': FLOP_PER_SAMPLE_CNL * float(np.mean(nsmp)),
-                         # the second MFMA kernel of the frame (rank 0's launches): algorithmic 200 704 FLOP per live sample
-                         # (91 520 MAC = 183 040 FLOP executed after folding the 69 per-frame condition inputs into a bias)
-                         'nonrigid': None if nr_ms is None else {
-                             'kernel': 'occ::nr16::nonrigid_lds_kernel', 'launch_ms': nr_ms,
-                             'achieved_algorithmic': FLOP_PER_SAMPLE_NR * live / (nr_ms * 1e-3) / 1e12,
-                             'frac_algorithmic': FLOP_PER_SAMPLE_NR * live / (nr_ms * 1e-3) / PEAK_FP32_MFMA,
-                             'frac_executed': 183040 * live / (nr_ms * 1e-3) / PEAK_FP32_MFMA},
-                         # whole step: canonical + non-rigid algorithmic FLOP of the samples rank 0 evaluated / step time
-                         'end_to_end_frac': (FLOP_PER_SAMPLE_CNL + FLOP_PER_SAMPLE_NR) * live / step_s / PEAK_FP32_MFMA},
         }
+        if roofline is not None:
+            line['roofline'] = roofline
         line.update(side)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle.chain import model_context                  # the checker, timed as the stated CPU baseline
             line['cpu_baseline'] = cpu_baseline(model_context(0, False), frame, args.cpu_rays)
         json_out.write(json.dumps(line) + '\n')

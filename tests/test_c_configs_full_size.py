@@ -311,7 +311,7 @@ def test_two_process_sharded_render_one_gpu():
     assert got['world_size_formed'] == 2 and got['backend'] == 'gloo'
     assert got['bit_identical'] and got['max_abs_diff'] == 0.0, got
     # and bench.py's N > 1 leg end to end (sharding, pipelined gather, max-over-ranks timing, weak_frames side figure)
-    line = _torchrun(['bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--no-cpu-baseline'], 2,
+    line = _torchrun(['bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline'], 2,
                      extra_env={'OCC_DIST_BACKEND': 'gloo', 'OCC_FORCE_DEVICE': '0'})
     assert line['n_gpus'] == 2 and line['scaling'] == 'strong' and line['config']['world_size_formed'] == 2
     assert line['value'] > 0 and line['weak_frames']['value'] > 0

@@ -27,7 +27,7 @@ def test_one_rank_rccl_group_runs_the_gather_path():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    res = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
+    res = subprocess.run([sys.executable, 'bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--full', '--no-cpu-baseline',
                           '--only', 'rccl_world1'], cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     import json

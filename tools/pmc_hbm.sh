@@ -10,8 +10,8 @@ out=$1
 export TMPDIR=/tmp
 d=gpurun_out/pmc_hbm
 mkdir -p $d
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $d/fetch -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt > $d/fetch.log 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $d/write -o p -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-alt > $d/write.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $d/fetch -o p -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-alt > $d/fetch.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $d/write -o p -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-alt > $d/write.log 2>&1
 python3 - $d $out <<'PY'
 import csv, glob, json, sys, collections
 d, out = sys.argv[1], sys.argv[2]
@@ -30,7 +30,7 @@ if line:
 GATHER = ('sample_features', 'msknn', 'sample_warp', 'knn_small', 'point_table', 'point_sdf', 'grid_forward', 'grid_backward',
           'assemble_image')
 res = {'source': 'tools/pmc_hbm.sh: rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), '
-                 'bench.py --steps 2 --warmup 1 on MI355X',
+                 'bench.py --steps 2 --warmup 1 --full on MI355X',
        'units': 'counter values are KiB per launch (mean over the launches); hbm_bytes_corrected = fetch_factor x FETCH_SIZE + '
                 'WRITE_SIZE with fetch_factor 2 for kernels that stream wide coalesced reads (MI355X_MICROARCH.md, HBM section) '
                 'and 1 for the gather kernels (profiles/archive/r03_fetch_calibration.md: 64-byte gather misses are counted at face value)',

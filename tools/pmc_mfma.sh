@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 d=gpurun_out/pmc_mfma
 mkdir -p $d
 legs=${2:---no-alt}
-args="bench.py --steps 2 --warmup 1 --no-cpu-baseline $legs"
+args="bench.py --steps 2 --warmup 1 --full --no-cpu-baseline $legs"
 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $d/p1 -o p -- python3 $args > $d/p1.log 2>&1
 rocprofv3 --pmc SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU --output-format csv -d $d/p2 -o p -- python3 $args > $d/p2.log 2>&1
 rocprofv3 --pmc GRBM_GUI_ACTIVE --output-format csv -d $d/p3 -o p -- python3 $args > $d/p3.log 2>&1
@@ -30,7 +30,7 @@ n = int(json.loads(line[-1])['config']['samples_evaluated_per_launch']) if line 
 SIMDS = 256 * 4
 XCDS = 8            # GRBM_GUI_ACTIVE comes back summed over the 8 XCDs (2.14e9 for a 113 ms launch = 8 x 2.37 GHz)
 res = {'source': 'tools/pmc_mfma.sh: three rocprofv3 --pmc passes (SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES | SQ_BUSY_CYCLES '
-                 'SQ_WAVE_CYCLES SQ_INSTS_VALU | GRBM_GUI_ACTIVE) of `python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline '
+                 'SQ_WAVE_CYCLES SQ_INSTS_VALU | GRBM_GUI_ACTIVE) of `python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline '
                  '--no-alt` on MI355X; means over the launches',
        'notes': 'SQ_VALU_MFMA_BUSY_CYCLES counts cycles summed over the SIMDs (MI355X_MICROARCH.md: = issue cycles x N_mfma); '
                 'mfma_busy_frac = SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs); one v_mfma_f32_16x16x4_f32 '

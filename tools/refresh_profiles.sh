@@ -6,7 +6,7 @@ tag=$1
 export TMPDIR=/tmp
 o=gpurun_out/$tag
 mkdir -p $o
-timeout -k 5 900 python3 bench.py > $o/bench_line.json 2> $o/bench.err
+timeout -k 5 900 python3 bench.py --full > $o/bench_line.json 2> $o/bench.err
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_bench -o b -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-alt > $o/prof_bench_line.json 2> $o/prof_bench.err
 cat > /tmp/dd_frame.py <<'PY'
 import sys, torch
