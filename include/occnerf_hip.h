@@ -623,6 +623,33 @@ int occnerf_adam_step(const void *table, int32_t n_tensors, const int32_t *chunk
                       int32_t chunk_elems, double beta1, double beta2, double eps, double max_grad_norm, float *scratch,
                       void *stream);
 
+/* LPIPS v0.1, VGG16 trunk (third_parties/lpips/lpips.py:23-124, pretrained_networks.py:96-134): the perceptual term of the
+ * reference's training objective (lossweights.lpips, trainer.py:92-106), forward and input gradient in exact fp32.
+ * occnerf_lpips_pack: h_conv_w[13] / h_conv_b[13] (HOST arrays of device pointers): the torch weights [Cout,Cin,3,3] and
+ *   biases of features.{0,2,5,7,10,12,14,17,19,21,24,26,28}; h_lin[5]: lin0..lin4 weights [1,C,1,1]; shift[3], scale[3]: the
+ *   scaling layer -> packed[occnerf_lpips_packed_floats()], the forward and data-gradient operand layouts.  Run once at load.
+ * occnerf_lpips_workspace_floats: size of the workspace of one forward/backward pair (-1 for sizes the network refuses).
+ * occnerf_lpips_forward: in0, in1 [N,3,H,W] (in_nhwc = 0) or [N,H,W,3] (in_nhwc = 1), H, W >= 16 -> val[N] and, when res is
+ *   not NULL, res[5,N] (the per-tap spatial means, retPerLayer).  pred and target run as one batch of 2N images.
+ * occnerf_lpips_backward: after the forward on the same workspace; gres[5,N] = d loss / d res (d loss / d val on every tap,
+ *   plus the per-tap cotangents) -> d_in0, d_in1 in the inputs' layout, either may be NULL (its half of the batch is skipped).
+ * Every pass is bitwise deterministic (split-K partials are summed in a fixed order, no float atomics). */
+int64_t occnerf_lpips_packed_floats(void);
+int64_t occnerf_lpips_workspace_floats(int32_t N, int32_t H, int32_t W);
+int occnerf_lpips_pack(const float *const *h_conv_w, const float *const *h_conv_b, const float *const *h_lin,
+                       const float *shift, const float *scale, float *packed, void *stream);
+int occnerf_lpips_forward(const float *packed, const float *in0, const float *in1, int32_t N, int32_t H, int32_t W,
+                          int32_t in_nhwc, float *work, float *val, float *res, void *stream);
+int occnerf_lpips_backward(const float *packed, float *work, int32_t N, int32_t H, int32_t W, int32_t in_nhwc,
+                           const float *gres, float *d_in0, float *d_in1, void *stream);
+
+/* Patch images of the training batch, trainer.py:31-41 (_unpack_imgs): img[P,S,S,3] = rgb[row_of_pix[p]] where the pixel has
+ * a ray, h_bgcolor01[3] (HOST, bgcolor / 255) elsewhere; row_of_pix[P*S*S] int32, -1 = no ray.  Its adjoint d_rgb[R,3] =
+ * d_img[pix_of_row[r]] (each row owns one pixel, so it is a gather). */
+int occnerf_patch_assemble(const float *rgb, const int32_t *row_of_pix, int64_t R, int32_t n_patches, int32_t size,
+                           const float *h_bgcolor01, float *img, void *stream);
+int occnerf_patch_assemble_backward(const float *d_img, const int32_t *pix_of_row, int64_t R, float *d_rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,13 @@ SIGNATURES = {
     'occnerf_convt3d_im2col': (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     'occnerf_adam_table_row_bytes': (_i32, []),
     'occnerf_adam_step': (C.c_int, [_vp, _i32, _vp, _i32, _i32] + [C.c_double] * 4 + [_vp, _vp]),
+    'occnerf_lpips_packed_floats': (_i64, []),
+    'occnerf_lpips_workspace_floats': (_i64, [_i32, _i32, _i32]),
+    'occnerf_lpips_pack': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'occnerf_lpips_forward': (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'occnerf_lpips_backward': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'occnerf_patch_assemble': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp]),
+    'occnerf_patch_assemble_backward': (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

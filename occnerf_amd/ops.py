@@ -905,3 +905,96 @@ def aggregate(feats, knn, atts):
     ids AND weights are bitwise identical are evaluated / scattered once (exact for arbitrary atts).  Limits of the backward,
     refused by name: K <= 64 neighbours, F <= 64 columns, P <= 32 x min(1024, 18432 // F) rows (16 832 at F = 35)."""
     return _Aggregate.apply(feats, knn.contiguous(), atts.contiguous())
+
+
+# ------------------------------------------------------------------ LPIPS (VGG16, v0.1) and the patch images of the batch
+def lpips_pack(conv_w, conv_b, lins, shift, scale):
+    """13 conv weights [Cout,Cin,3,3] / biases, 5 lin weights [1,C,1,1], the scaling layer's shift / scale -> the packed blob
+    of occnerf_lpips_forward / _backward (forward and data-gradient operand layouts)."""
+    dev = conv_w[0].device
+    packed = torch.empty(int(_lib.lib().occnerf_lpips_packed_floats()), device=dev, dtype=torch.float32)
+    w = [t.detach().contiguous() for t in conv_w]
+    b = [t.detach().contiguous() for t in conv_b]
+    li = [t.detach().contiguous() for t in lins]
+    sh, sc = shift.detach().contiguous(), scale.detach().contiguous()
+    if len(w) != 13 or len(b) != 13 or len(li) != 5:
+        raise RuntimeError('lpips_pack: needs 13 conv weights, 13 conv biases and 5 lin weights')
+    with _guard_dev(dev):
+        hw, hb, hl = _ptr_table(w, 'conv weight'), _ptr_table(b, 'conv bias'), _ptr_table(li, 'lin weight')
+        rc = _lib.lib().occnerf_lpips_pack(hw, hb, hl, _chk(sh, torch.float32, 'shift'), _chk(sc, torch.float32, 'scale'),
+                                           packed.data_ptr(), _stream(packed))
+    _lib.check(rc, 'lpips_pack')
+    return packed
+
+
+def _lpips_layout(in0, in1):
+    """(in0, in1, nhwc): NCHW-contiguous inputs as they are, NHWC-dense ones (a permuted [N,H,W,3] tensor) without a copy."""
+    if in0.is_contiguous() and in1.is_contiguous():
+        return in0, in1, 0
+    p0, p1 = in0.permute(0, 2, 3, 1), in1.permute(0, 2, 3, 1)
+    if p0.is_contiguous() and p1.is_contiguous():
+        return in0, in1, 1
+    return in0.contiguous(), in1.contiguous(), 0
+
+
+def lpips_forward(packed, in0, in1, want_res=False):
+    """val[N] (and res[5,N]) of LPIPS-VGG for in0, in1 [N,3,H,W]; returns (val, res, work, nhwc) -- the workspace carries the
+    activations the backward needs."""
+    if in0.dim() != 4 or in0.shape != in1.shape or in0.shape[1] != 3:
+        raise RuntimeError(f'lpips: in0 and in1 must both be [N,3,H,W], got {tuple(in0.shape)} and {tuple(in1.shape)}')
+    N, _, H, W = in0.shape
+    in0, in1, nhwc = _lpips_layout(in0, in1)
+    with _guard(in0):
+        nw = int(_lib.lib().occnerf_lpips_workspace_floats(N, H, W))
+        if nw < 0:
+            raise RuntimeError(f'lpips: H and W must be >= 16 so that relu5_3 is not empty (got {H} x {W}), N >= 1')
+        work = torch.empty(nw, device=in0.device, dtype=torch.float32)
+        val = torch.empty(N, device=in0.device, dtype=torch.float32)
+        res = torch.empty(5, N, device=in0.device, dtype=torch.float32) if want_res else None
+        a0 = _chk(in0.permute(0, 2, 3, 1) if nhwc else in0, torch.float32, 'in0')
+        a1 = _chk(in1.permute(0, 2, 3, 1) if nhwc else in1, torch.float32, 'in1')
+        rc = _lib.lib().occnerf_lpips_forward(_chk(packed, torch.float32, 'packed'), a0, a1, N, H, W, nhwc, work.data_ptr(),
+                                              val.data_ptr(), None if res is None else res.data_ptr(), _stream(in0))
+    _lib.check(rc, 'lpips_forward')
+    return val, res, work, nhwc
+
+
+def lpips_backward(packed, work, shape, nhwc, gres, need0, need1):
+    """d in0 / d in1 (None where not needed) from gres[5,N] = d loss / d res, on the workspace of the matching forward."""
+    N, _, H, W = shape
+
+    def alloc():
+        return torch.empty((N, H, W, 3) if nhwc else (N, 3, H, W), device=work.device, dtype=torch.float32)
+    d0 = alloc() if need0 else None
+    d1 = alloc() if need1 else None
+    with _guard(work):
+        rc = _lib.lib().occnerf_lpips_backward(_chk(packed, torch.float32, 'packed'), _chk(work, torch.float32, 'work'), N,
+                                               H, W, nhwc, _chk(gres, torch.float32, 'gres'),
+                                               None if d0 is None else d0.data_ptr(), None if d1 is None else d1.data_ptr(),
+                                               _stream(work))
+    _lib.check(rc, 'lpips_backward')
+    fix = (lambda t: None if t is None else t.permute(0, 3, 1, 2)) if nhwc else (lambda t: t)
+    return fix(d0), fix(d1)
+
+
+def patch_assemble(rgb, row_of_pix, n_patches, size, bgcolor01):
+    """img[P,S,S,3] from the batch's rows (trainer.py:31-41 _unpack_imgs), background bgcolor01 where a pixel has no ray."""
+    R = rgb.shape[0]
+    img = torch.empty(n_patches, size, size, 3, device=rgb.device, dtype=torch.float32)
+    bg, bgp = _host_f32(bgcolor01, 3)
+    with _guard(rgb):
+        rc = _lib.lib().occnerf_patch_assemble(_chk(rgb, torch.float32, 'rgb'), _chk(row_of_pix, torch.int32, 'row_of_pix'),
+                                               R, int(n_patches), int(size), bgp, img.data_ptr(), _stream(rgb))
+    _lib.check(rc, 'patch_assemble')
+    return img
+
+
+def patch_assemble_backward(d_img, pix_of_row):
+    R = pix_of_row.shape[0]
+    d_rgb = torch.empty(R, 3, device=d_img.device, dtype=torch.float32)
+    with _guard(d_img):
+        rc = _lib.lib().occnerf_patch_assemble_backward(_chk(d_img, torch.float32, 'd_img'),
+                                                        _chk(pix_of_row, torch.int32, 'pix_of_row'), R, d_rgb.data_ptr(),
+                                                        _stream(d_img))
+    _lib.check(rc, 'patch_assemble_backward')
+    return d_rgb

@@ -44,16 +44,13 @@ def host_frame(frame):
     return {k: torch.from_numpy(np.ascontiguousarray(frame[k])).pin_memory() for k in FRAME_KEYS}
 
 
-def patch_ray_selection(frame, rng, n_patches=6, size=32, full=False):
-    """Ray indices (into the frame's bbox-hitting ray list) of `n_patches` random size x size pixel patches -- the training
-    batch of the reference (configs/default.yaml:147-150 `patch`, core/data/human_nerf/train.py sample_patch_rays): a patch
-    counts when more than half of its pixels hit the bbox (`full`: all of them, which fixes the batch at n_patches x size^2
-    rays -- the benchmark's 6 x 32 x 32 = 6 144); patches may overlap, as the reference's do."""
+def _draw_patches(frame, rng, n_patches, size, full):
+    """(ray indices, row-major positions inside the patch) of each accepted patch, in draw order."""
     H = W = int(frame['img_width'])
     index_of = -np.ones(H * W, dtype=np.int64)
     index_of[np.nonzero(np.asarray(frame['ray_mask']).reshape(-1))[0]] = np.arange(frame['rays'].shape[1])
-    sel, tries = [], 0
-    while len(sel) < n_patches:
+    out, tries = [], 0
+    while len(out) < n_patches:
         tries += 1
         if tries > 100000:
             raise RuntimeError('patch_ray_selection: no patch of this size fits the rays of the frame')
@@ -61,6 +58,23 @@ def patch_ray_selection(frame, rng, n_patches=6, size=32, full=False):
         pix = (np.arange(y, y + size)[:, None] * W + np.arange(x, x + size)[None, :]).ravel()
         rays = index_of[pix]
         if (rays >= 0).all() if full else (rays >= 0).mean() > 0.5:
-            sel.append(rays[rays >= 0])
-    return np.concatenate(sel)
+            out.append((rays[rays >= 0], np.nonzero(rays >= 0)[0]))
+    return out
 
+
+def patch_ray_selection(frame, rng, n_patches=6, size=32, full=False):
+    """Ray indices (into the frame's bbox-hitting ray list) of `n_patches` random size x size pixel patches -- the training
+    batch of the reference (configs/default.yaml:147-150 `patch`, core/data/human_nerf/train.py sample_patch_rays): a patch
+    counts when more than half of its pixels hit the bbox (`full`: all of them, which fixes the batch at n_patches x size^2
+    rays -- the benchmark's 6 x 32 x 32 = 6 144); patches may overlap, as the reference's do."""
+    return np.concatenate([rays for rays, _ in _draw_patches(frame, rng, n_patches, size, full)])
+
+
+def patch_ray_selection_map(frame, rng, n_patches=6, size=32, full=False):
+    """patch_ray_selection (same draws, same rays) plus each row's pixel in the patch images: pix[R] = patch * size^2 +
+    y * size + x -- the reference's patch_masks / patch_div_indices (trainer.py:31-41) as one row -> pixel map.  A ray inside
+    two overlapping patches appears as two rows, one per patch, so rows and covered pixels are in bijection."""
+    drawn = _draw_patches(frame, rng, n_patches, size, full)
+    sel = np.concatenate([rays for rays, _ in drawn])
+    pix = np.concatenate([i * size * size + pos for i, (_, pos) in enumerate(drawn)]).astype(np.int64)
+    return sel, pix

@@ -6,9 +6,17 @@ Scope: one optimisation step = Networ
 training mode through the differentiable path (occnerf_amd/train_path.py: torch autograd over
 the HIP kNN and the HIP grid-encoder forward/backward) + MSE and completeness losses +
 clip_grad_norm + Adam with the reference's per-group learning rates (optimizer.py:12-43) +
-exponential decay (exp_decay.py:7-19).  LPIPS, real datasets and progress dumps are out of scope;
-the supervision here is a synthetic teacher (the same network with a second seeded checkpoint)
-rendered through the HIP path.  Checkpoints use the reference's layout
+exponential decay (exp_decay.py:7-19).  Real datasets and progress dumps are out of scope; the
+supervision here is a synthetic teacher (the same network with a second seeded checkpoint) rendered
+through the HIP path.
+
+`train.lossweights` containing `lpips` switches on the reference's objective (trainer.py:92-106,
+135-200): predicted and teacher rays are assembled into the patch images (trainer.py:31-41), and
+mse * MSE + lpips * mean(LPIPS-VGG) on those images (inputs scaled to [-1, 1]) + comp is minimised,
+e.g. `train.lossweights "{'lpips': 1.0, 'mse': 0.2, 'comp': 1.0}"`.  LPIPS runs on the HIP kernels of
+occnerf_amd/lpips.py; its weights come from train.lpips_model_path (the v0.1 vgg.pth lin layers) and
+train.lpips_vgg16_path (a torchvision VGG16 state_dict), each a seeded stand-in when unset.  Without
+`lpips` the step is the ray-wise MSE + comp one.  Checkpoints use the reference's layout
 ({'iter','network','optimizer'} -> experiments/.../latest.tar, trainer.py:398-406)."""
 import os
 import time
@@ -25,7 +33,8 @@ LR_GROUPS = (('mweight_vol_decoder', 'lr_mweight_vol_decoder'), ('pose_decoder',
              ('non_rigid_mlp', 'lr_non_rigid_mlp'), ('point_dist', 'lr_point_dist'))
 TRAIN_DEFAULTS = {'maxiter': 100, 'lr': 5e-4, 'lr_point_dist': 1e-4, 'lr_mweight_vol_decoder': 5e-5,
                   'lr_pose_decoder': 5e-5, 'lr_non_rigid_mlp': 5e-5, 'lrate_decay': 500, 'log_interval': 10,
-                  'bf16': False, 'lossweights': {'mse': 0.2, 'comp': 1.0}}
+                  'bf16': False, 'lossweights': {'mse': 0.2, 'comp': 1.0},
+                  'lpips_model_path': None, 'lpips_vgg16_path': None}
 
 
 def make_optimizer(net, tc):
@@ -65,11 +74,21 @@ def main():
     rng = np.random.RandomState(0)
     size = int(cfg.get('render_size', 256))
     os.makedirs(cfg.logdir, exist_ok=True)
+    use_lpips = 'lpips' in tc['lossweights']
+    if use_lpips:
+        from occnerf_amd.lpips import PatchImages, make_training_lpips, patch_image_loss
+        from occnerf_amd.seeded import patch_ray_selection_map
+        lpips, what = make_training_lpips(tc['lpips_model_path'], tc['lpips_vgg16_path'], dev)
+        print(what)
     t0 = time.time()
     for it in range(1, int(tc['maxiter']) + 1):
         frame = synth.make_frame(img_size=size, pose72=synth.seeded_pose(100 + it % 16), orbit_frame=it % 50,
                                  orbit_period=50, bgcolor=cfg.bgcolor)
-        sel = patch_rays(frame, rng, int(cfg.patch.N_patches), int(cfg.patch.size))
+        if use_lpips:
+            sel, pix = patch_ray_selection_map(frame, rng, int(cfg.patch.N_patches), int(cfg.patch.size))
+            patches = PatchImages(pix, int(cfg.patch.N_patches), int(cfg.patch.size), dev)
+        else:
+            sel = patch_rays(frame, rng, int(cfg.patch.N_patches), int(cfg.patch.size))
         frame['rays'], frame['near'], frame['far'] = frame['rays'][:, sel], frame['near'][sel], frame['far'][sel]
         keys = ['rays', 'near', 'far', 'bgcolor', 'dst_Rs', 'dst_Ts', 'cnl_gtfms', 'motion_weights_priors',
                 'cnl_bbox_min_xyz', 'cnl_bbox_max_xyz', 'cnl_bbox_scale_xyz', 'dst_posevec']
@@ -79,8 +98,12 @@ def main():
         opt.zero_grad(set_to_none=True)
         with torch.autocast('cuda', dtype=torch.bfloat16, enabled=bool(tc['bf16'])):
             out = net(**data, iter_val=it)
-            loss = tc['lossweights']['mse'] * torch.mean((out['rgb'].float() - target) ** 2) \
-                + tc['lossweights']['comp'] * out['comp_loss'].float().mean()
+            if use_lpips:
+                loss = patch_image_loss(out['rgb'], target, patches, frame['bgcolor'] / 255., tc['lossweights'], lpips) \
+                    + tc['lossweights'].get('comp', 1.0) * out['comp_loss'].float().mean()
+            else:
+                loss = tc['lossweights']['mse'] * torch.mean((out['rgb'].float() - target) ** 2) \
+                    + tc['lossweights']['comp'] * out['comp_loss'].float().mean()
         loss.backward()
         opt.step(max_grad_norm=1.0)                                     # trainer.py:248-249: clip + Adam, one device pass
         decay = 0.1 ** (it / (tc['lrate_decay'] * 1000))                # exp_decay.py:7-19
