@@ -17,7 +17,10 @@
  * `_gridencoder` pybind module).  Section 2 are the fused stages that sit behind the
  * reference's *module* seam (core/nets/occnerf/network.py `Network`,
  * canonical_mlps/occnerf_mlp.py `CanonicalMLP`): the reference evaluates them as chains
- * of torch ops and has no FFI for them; each entry cites the Python it replaces.
+ * of torch ops and has no FFI for them; each entry cites the Python it replaces.  The
+ * last entries serve the reference's scripts around the renderer: LPIPS for training, the
+ * patch images, and eval.py's per-frame metrics (SSIM / PSNR / IoU, which the reference
+ * takes from skimage and numpy on the host).
  */
 #ifndef OCCNERF_HIP_H
 #define OCCNERF_HIP_H
@@ -649,6 +652,26 @@ int occnerf_lpips_backward(const float *packed, float *work, int32_t N, int32_t 
 int occnerf_patch_assemble(const float *rgb, const int32_t *row_of_pix, int64_t R, int32_t n_patches, int32_t size,
                            const float *h_bgcolor01, float *img, void *stream);
 int occnerf_patch_assemble_backward(const float *d_img, const int32_t *pix_of_row, int64_t R, float *d_rgb, void *stream);
+
+/* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
+ * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
+ * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance
+ * (49/48), K1 = 0.01, K2 = 0.03, C = (K data_range)^2 (eval.py's float64 images give data_range = 2), evaluated in fp64
+ * from exact integer box moments.
+ * pred, truth [N,H,W,3] uint8; alpha [N,H,W] float32 (the predicted alpha map, 0 where no ray); body [N,H,W] uint8
+ * (ray_mask); gt_vis_alpha [N,H,W] float32 (ray_alpha scattered by ray_mask) or NULL; gt_alpha [N,H,W] float32 (the gt
+ * alpha image's channel 0) or NULL.  alpha / body NULL: empty masks.  Masks, compared in float32: vis = gt_vis_alpha > 0.5
+ * when given, else alpha > 0.001; IoU = |(alpha > 0.1) & (gt_alpha > 0.5)| / |... or ...| (gt_alpha NULL: nan).
+ * record[N, OCCNERF_FRAME_METRICS_RECORD] fp64: psnr_vis, ssim_vis, psnr_body, ssim_body, psnr_full, ssim_full (mssim: the
+ * mean with 3 pixels cropped from each edge), iou, then n_vis, n_body, intersection, union (pixels) and the squared-error
+ * sums over vis, body, full (8-bit units, all channels).  Empty selections give nan, a zero error inf, as numpy does.
+ * ssim_map [N,H,W,3] fp64 (optional): the full S map.  workspace: occnerf_frame_metrics_workspace_bytes(N, H, W) bytes
+ * (-1 for sizes the kernel refuses).  Bitwise deterministic (fixed-order sums, no atomics). */
+#define OCCNERF_FRAME_METRICS_RECORD 14
+int64_t occnerf_frame_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int occnerf_frame_metrics(const uint8_t *pred, const uint8_t *truth, const float *alpha, const uint8_t *body,
+                          const float *gt_vis_alpha, const float *gt_alpha, int32_t N, int32_t H, int32_t W,
+                          double data_range, double *record, double *ssim_map, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,8 @@ _DEFAULTS = {
     'bgcolor': [0.0, 0.0, 0.0], 'resize_img_scale': 0.5, 'show_alpha': False, 'show_truth': False,
     'patch': {'sample_subject_ratio': 0.8, 'N_patches': 6, 'size': 32},
     'freeview': {'frame_idx': 0}, 'tpose': {}, 'movement': {}, 'train': {},
+    # eval.py: `eval.lpips True` adds an LPIPS column (weights: the LPIPS model_path / vgg16_path, else the seeded trunk)
+    'eval': {'lpips': False, 'lpips_model_path': None, 'lpips_vgg16_path': None},
     # build-specific keys
     'smpl_model': 'auto',            # 'auto' | 'synthetic' | directory holding the SMPL pickles
     # samples resident per pipeline pass (~470 B each): 2^28 keeps a whole 1024^2 x 192 frame (141 M samples, 63 GiB peak of the

@@ -152,21 +152,27 @@ def run_allview():
     _render('allview', f'allview_{cfg.freeview.frame_idx}' if not cfg.render_folder_name else cfg.render_folder_name)
 
 
-def run_evaluate():
-    """run.py:194-244: PSNR of the rendered rays against the frames' target colours over the `progress` frames (frames
-    4 and 15 skipped, the network called with iter_val = 1 exactly as the reference does, run.py:224-230: pose refinement
-    and the non-rigid condition are then below their kick-in iterations).  The
-    synthetic source has no photographs: its targets are a teacher's render of the same rays (the seeded, amplified
-    checkpoint `cfg.evaluate_teacher`, like train.py's supervision).  Metrics beyond PSNR are out of scope."""
+def _teacher(loader, dev):
+    """The synthetic source has no photographs: its targets are a teacher's render of the same rays, the seeded, amplified
+    checkpoint (seed `cfg.evaluate_teacher_seed`, default 1), like train.py's supervision.  -> its ShardedRenderer."""
     from occnerf_amd.checkpoint import make_state_dict
-    rank, world, model, loader, renderer, dev = _setup('progress', evaluate=True)
     teacher = create_network()
     teacher.generate_neural_points(loader.dataset.avg_betas)
     seed = int(cfg.get('evaluate_teacher_seed', 1))
     teacher.load_state_dict(make_state_dict(teacher.point_base.detach().numpy(), float(teacher.bound), seed=seed,
                                             amplify=True), strict=True)
     teacher = teacher.to(dev).eval()
-    teach = ShardedRenderer(teacher, dev)
+    return ShardedRenderer(teacher, dev)
+
+
+def run_evaluate():
+    """run.py:194-244: PSNR of the rendered rays against the frames' target colours over the `progress` frames (frames
+    4 and 15 skipped, the network called with iter_val = 1 exactly as the reference does, run.py:224-230: pose refinement
+    and the non-rigid condition are then below their kick-in iterations).  The targets are the teacher's render
+    (`_teacher`).  The paper's metrics -- PSNR and SSIM over the vis / body / full pixels and the silhouette IoU, the
+    reference's eval.py -- are computed by eval.py at the repository root."""
+    rank, world, model, loader, renderer, dev = _setup('progress', evaluate=True)
+    teach = _teacher(loader, dev)
     psnrs, skips = [], [4, 15]
     with torch.no_grad():
         for data, key, meta in frames_to_device(loader, 'progress', dev):
