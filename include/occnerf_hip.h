@@ -57,8 +57,7 @@ int occnerf_experiment_knob(const char *name, int value);
  *    D in {2,3,4,5}, C in {1,2,4,8}.  The reference dispatches on the tensors' dtype
  *    (AT_DISPATCH_FLOATING_TYPES_AND_HALF, gridencoder.cu:467,500); a C ABI has no tensor to
  *    ask, so the dtype is in the entry point's name: no suffix = float32 (what the rendering
- *    path uses), _f16 = at::Half (what grid.py:44-45 feeds under autocast).  float64 is not
- *    built (nothing on the path produces double embeddings).
+ *    path uses), _f16 = at::Half (what grid.py:44-45 feeds under autocast), _f64 = double.
  * ---------------------------------------------------------------------------------- */
 
 /* inputs[B,D] in [0,1] (rows outside -> zeros); embeddings[sO,C]; offsets[L+1] int32;
@@ -111,9 +110,9 @@ int occnerf_grid_encode_backward_h(const float *grad, const float *inputs, const
 /* The at::Half dispatch case of the two operators above (gridencoder.cu:467,500).  embeddings, outputs, dy_dx, grad,
  * grad_embeddings, grad_inputs are IEEE binary16 arrays (torch.half); inputs stay float32, as in the reference
  * (`const float *inputs`, gridencoder.cu:373).  Arithmetic follows c10::Half exactly: cell position and corner weights in
- * float, every `scalar_t +=` a half-rounded term added in float and rounded to half (occnerf_amd/csrc/grid_encode_f16.hip
- * spells it out); the backward adds channel pairs with packed-half atomics (gridencoder.cu:323-331), so C must be even
- * there -- the reference's own C = 1 half path is an empty stub (:22-26) and grid.py:44 never selects it. */
+ * float, every `scalar_t +=` a half-rounded term added in float and rounded to half (GridMath<half_t> in
+ * occnerf_amd/csrc/grid_encode.hip spells it out); the backward adds channel pairs with packed-half atomics
+ * (gridencoder.cu:323-331), so C must be even there -- the reference's own C = 1 half path is an empty stub (:22-26) and grid.py:44 never selects it. */
 int occnerf_grid_encode_forward_f16(const float *inputs, const void *embeddings, const int32_t *offsets, void *outputs,
                                     uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void *dy_dx,
                                     uint32_t gridtype, int align_corners, uint32_t interp, void *stream);
@@ -125,8 +124,8 @@ int occnerf_grid_encode_backward_f16(const void *grad, const float *inputs, cons
 /* The double dispatch case (gridencoder.cu:467,500 with scalar_t = double): embeddings, outputs, dy_dx, grad, grad_embeddings,
  * grad_inputs are float64; inputs stay float32 and so do the cell position, the corner weights and pos_deriv, exactly as the
  * reference's templates leave them; products with the double tensors are formed in double and `r += a * b` is one fma
- * (csrc/grid_encode_f64.hip).  The backward scatters with global_atomic_add_f64.  With the two calls above this completes
- * AT_DISPATCH_FLOATING_TYPES_AND_HALF: no dtype the reference's `_gridencoder` accepts is refused. */
+ * (GridMath<double> in csrc/grid_encode.hip).  The backward scatters with global_atomic_add_f64.  With the two calls above
+ * this completes AT_DISPATCH_FLOATING_TYPES_AND_HALF: no dtype the reference's `_gridencoder` accepts is refused. */
 int occnerf_grid_encode_forward_f64(const float *inputs, const double *embeddings, const int32_t *offsets, double *outputs,
                                     uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, double *dy_dx,
                                     uint32_t gridtype, int align_corners, uint32_t interp, void *stream);

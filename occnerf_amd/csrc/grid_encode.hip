@@ -1,7 +1,9 @@
 // Multi-resolution hash-grid encoder for gfx950: forward (+dy_dx), backward, TV stub.
 //
 // Operator-level replacement of the reference's `_gridencoder` extension
-// (core/nets/occnerf/gridencoder/src/gridencoder.cu:87-369, bindings.cpp:5-9).
+// (core/nets/occnerf/gridencoder/src/gridencoder.cu:87-369, bindings.cpp:5-9), for all three dtypes of its
+// AT_DISPATCH_FLOATING_TYPES_AND_HALF (gridencoder.cu:467,500): one set of generic kernels templated on the storage type,
+// plus the D = 4, C = 2 fp32 kernels of the training step.
 // The sample pipeline does not call these kernels for its 33 M samples per frame -- it
 // uses the fused occ::encode_level_d4c2 inside sample_features.hip -- but the operator is
 // the reference's native seam for this path, and the per-point table build, the training
@@ -13,24 +15,118 @@
 // [L,B,C] output layout, so that concurrently running blocks work on the same level.
 #include "common.h"
 
+#include <type_traits>
 #include <vector>
 
 namespace occ {
 
-template <uint32_t D, uint32_t C>
+typedef _Float16 half_t;
+typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+
+// c10::Half(float): the float VALUE is rounded to half (__float2half_rn).  Left to itself hipcc folds
+// `(half)(a * b)` into v_fma_mixlo_f16, which rounds the exact product once (and returns +0 for w * -0): measured on gfx950,
+// 1 382 of 2^24 random products differ from multiply-in-float-then-convert.  The empty asm pins the float value first.
+__device__ __forceinline__ half_t to_half(float v) {
+    asm volatile("" : "+v"(v));
+    return (half_t)v;
+}
+__device__ __forceinline__ half_t hadd(half_t a, half_t b) { return to_half((float)a + (float)b); }   // c10 Half + Half
+
+// What scalar_t means in the reference's templates, per dispatched storage type T (embeddings, outputs, dy_dx and the
+// gradients).  inputs, the cell position, the corner weights w and pos_deriv stay float for every T (data_ptr<float>(),
+// gridencoder.cu:470; float arithmetic, :141-180); only these terms differ:
+//   corner      forward (:166-197): one corner's term, added in corner order
+//   dydx        dy_dx (:201-244): gr / gl are the upper / lower corner along the derivative's axis
+//   scatter     backward (:305-339): adds kAtomic consecutive channels of one corner with one atomic; a backward thread
+//               covers per_thread(C) channels
+//   input_grad  input backward (:343-369)
+template <typename T>
+struct GridMath;
+
+// float: `r += w * g` is one fma (nvcc contracts it); the input gradient stays a separate multiply and add, as the library
+// builds with -ffp-contract=off.
+template <>
+struct GridMath<float> {
+    static constexpr uint32_t per_thread(uint32_t C) { return C; }
+    static constexpr uint32_t kAtomic = 1;
+    static __device__ __forceinline__ float corner(float acc, float w, float g) { return __fmaf_rn(w, g, acc); }
+    static __device__ __forceinline__ float dydx(float acc, float w, float gr, float gl, float pos_deriv) {
+        return __fmaf_rn(__fmul_rn(w, __fsub_rn(gr, gl)), pos_deriv, acc);
+    }
+    static __device__ __forceinline__ void scatter(float *p, float w, const float *g) { atomicAdd(p, __fmul_rn(w, *g)); }
+    static __device__ __forceinline__ float input_grad(float r, float g, float dy) { return r + g * dy; }
+};
+
+// double: every product with a double tensor is formed in double (usual arithmetic conversions), nvcc contracting
+// `r += a * b` into one fma; the backward scatters with global_atomic_add_f64.
+template <>
+struct GridMath<double> {
+    static constexpr uint32_t per_thread(uint32_t C) { return C; }
+    static constexpr uint32_t kAtomic = 1;
+    static __device__ __forceinline__ double corner(double acc, float w, double g) { return __fma_rn((double)w, g, acc); }
+    static __device__ __forceinline__ double dydx(double acc, float w, double gr, double gl, float pos_deriv) {
+        return __fma_rn(__dmul_rn((double)w, __dsub_rn(gr, gl)), (double)pos_deriv, acc);
+    }
+    static __device__ __forceinline__ void scatter(double *p, float w, const double *g) {
+        unsafeAtomicAdd(p, __dmul_rn((double)w, *g));
+    }
+    static __device__ __forceinline__ double input_grad(double r, double g, double dy) { return __fma_rn(g, dy, r); }
+};
+
+// at::Half (c10/util/Half-inl.h): every Half operator computes in float and rounds the result to half; `Half += float`
+// converts the float operand to Half first.  The backward adds channel pairs with one packed-half atomic
+// (`atomicAdd((__half2*)...)`; here global_atomic_pk_add_f16), so C must be even, as grid.py guarantees.
+template <>
+struct GridMath<half_t> {
+    static constexpr uint32_t per_thread(uint32_t) { return 2; }
+    static constexpr uint32_t kAtomic = 2;
+    static __device__ __forceinline__ half_t corner(half_t acc, float w, half_t g) {
+        return hadd(acc, to_half(__fmul_rn(w, (float)g)));
+    }
+    static __device__ __forceinline__ half_t dydx(half_t acc, float w, half_t gr, half_t gl, float pos_deriv) {
+        const half_t diff = to_half((float)gr - (float)gl);
+        return hadd(acc, to_half(__fmul_rn(__fmul_rn(w, (float)diff), pos_deriv)));
+    }
+    static __device__ __forceinline__ void scatter(half_t *p, float w, const half_t *g) {
+        const half2_t v = {to_half(__fmul_rn(w, (float)g[0])), to_half(__fmul_rn(w, (float)g[1]))};
+        __builtin_amdgcn_global_atomic_fadd_v2f16(
+            reinterpret_cast<__attribute__((address_space(1))) half2_t *>(reinterpret_cast<uintptr_t>(p)), v);
+    }
+    static __device__ __forceinline__ half_t input_grad(half_t r, half_t g, half_t dy) {
+        return hadd(r, to_half(__fmul_rn((float)g, (float)dy)));
+    }
+};
+
+// gridencoder.cu:141-159: one axis of the cell -- grid position pg, fraction pos (smoothstep for interp 1), d pos / d x.
+__device__ __forceinline__ void grid_cell_axis(float x, float scale, bool align_corners, uint32_t interp, float &pos,
+                                               float &pos_deriv, uint32_t &pg) {
+    pos = __fmaf_rn(x, scale, align_corners ? 0.0f : 0.5f);
+    const float fl = floorf(pos);
+    pg = (uint32_t)fl;
+    pos -= fl;
+    if (interp == 1) {
+        pos_deriv = __fmul_rn(__fmul_rn(6.f, pos), __fsub_rn(1.0f, pos));
+        pos = __fmul_rn(__fmul_rn(pos, pos), __fsub_rn(3.0f, __fmul_rn(2.0f, pos)));
+    } else {
+        pos_deriv = 1.0f;
+    }
+}
+
+template <typename T, uint32_t D, uint32_t C>
 __global__ __launch_bounds__(256) void grid_forward_kernel(
-    const float *__restrict__ inputs, const float *__restrict__ embeddings,
-    const int32_t *__restrict__ offsets, float *__restrict__ outputs, uint32_t B, uint32_t L,
-    GridLevels lv, float *__restrict__ dy_dx, uint32_t gridtype, bool align_corners,
+    const float *__restrict__ inputs, const T *__restrict__ embeddings,
+    const int32_t *__restrict__ offsets, T *__restrict__ outputs, uint32_t B, uint32_t L,
+    GridLevels lv, T *__restrict__ dy_dx, uint32_t gridtype, bool align_corners,
     uint32_t interp) {
+    using M = GridMath<T>;
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const uint32_t level = blockIdx.y;
 
-    const float *grid = embeddings + (size_t)(uint32_t)offsets[level] * C;
+    const T *grid = embeddings + (size_t)(uint32_t)offsets[level] * C;
     const float *x = inputs + (size_t)b * D;
-    float *out = outputs + ((size_t)level * B + b) * C;
-    float *dyl = dy_dx ? dy_dx + ((size_t)b * L + level) * D * C : nullptr;
+    T *out = outputs + ((size_t)level * B + b) * C;
+    T *dyl = dy_dx ? dy_dx + ((size_t)b * L + level) * D * C : nullptr;
 
     float xin[D];
     bool oob = false;
@@ -41,10 +137,10 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(
     }
     if (oob) {  // gridencoder.cu:118-135: rows outside [0,1] encode to zero
 #pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) out[ch] = 0.f;
+        for (uint32_t ch = 0; ch < C; ch++) out[ch] = T(0);
         if (dyl) {
 #pragma unroll
-            for (uint32_t i = 0; i < D * C; i++) dyl[i] = 0.f;
+            for (uint32_t i = 0; i < D * C; i++) dyl[i] = T(0);
         }
         return;
     }
@@ -56,23 +152,11 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(
     float pos[D], pos_deriv[D];
     uint32_t pg[D];
 #pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        pos[d] = __fmaf_rn(xin[d], scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= fl;
-        if (interp == 1) {
-            pos_deriv[d] = __fmul_rn(__fmul_rn(6.f, pos[d]), __fsub_rn(1.0f, pos[d]));
-            pos[d] = __fmul_rn(__fmul_rn(pos[d], pos[d]),
-                               __fsub_rn(3.0f, __fmul_rn(2.0f, pos[d])));
-        } else {
-            pos_deriv[d] = 1.0f;
-        }
-    }
+    for (uint32_t d = 0; d < D; d++) grid_cell_axis(xin[d], scale, align_corners, interp, pos[d], pos_deriv[d], pg[d]);
 
-    float results[C];
+    T results[C];
 #pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) results[ch] = 0.f;
+    for (uint32_t ch = 0; ch < C; ch++) results[ch] = T(0);
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
         float w = 1.f;
@@ -89,7 +173,7 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(
         }
         const uint32_t index = grid_index<D>(gridtype, align_corners, hashmap_size, resolution, pl) * C;
 #pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) results[ch] = __fmaf_rn(w, grid[index + ch], results[ch]);
+        for (uint32_t ch = 0; ch < C; ch++) results[ch] = M::corner(results[ch], w, grid[index + ch]);
     }
 #pragma unroll
     for (uint32_t ch = 0; ch < C; ch++) out[ch] = results[ch];
@@ -97,9 +181,9 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(
     if (dyl) {  // gridencoder.cu:201-244
 #pragma unroll
         for (uint32_t gd = 0; gd < D; gd++) {
-            float rg[C];
+            T rg[C];
 #pragma unroll
-            for (uint32_t ch = 0; ch < C; ch++) rg[ch] = 0.f;
+            for (uint32_t ch = 0; ch < C; ch++) rg[ch] = T(0);
 #pragma unroll
             for (uint32_t idx = 0; idx < (1u << (D - 1)); idx++) {
                 float w = scale;
@@ -120,9 +204,7 @@ __global__ __launch_bounds__(256) void grid_forward_kernel(
                 pl[gd] = pg[gd] + 1;
                 const uint32_t ir = grid_index<D>(gridtype, align_corners, hashmap_size, resolution, pl) * C;
 #pragma unroll
-                for (uint32_t ch = 0; ch < C; ch++)
-                    rg[ch] = __fmaf_rn(__fmul_rn(w, __fsub_rn(grid[ir + ch], grid[il + ch])),
-                                       pos_deriv[gd], rg[ch]);
+                for (uint32_t ch = 0; ch < C; ch++) rg[ch] = M::dydx(rg[ch], w, grid[ir + ch], grid[il + ch], pos_deriv[gd]);
             }
 #pragma unroll
             for (uint32_t ch = 0; ch < C; ch++) dyl[gd * C + ch] = rg[ch];
@@ -193,40 +275,40 @@ __global__ __launch_bounds__(256) void grid_forward_d4c2_kernel(const float4 *__
     }
 }
 
-// gridencoder.cu:248-340.  One thread per (sample, level); all C channels of a corner are
-// added by the same thread (C <= 8), fp32 atomics into the zero-initialised gradient table.  (Used for small
-// batches and the general D/C/gridtype cases; large D = 4, C = 2 batches take the tiled kernel below.)
-template <uint32_t D, uint32_t C>
+// gridencoder.cu:248-340.  One thread per (sample, level, per_thread(C) channels): all C channels of a corner for float and
+// double (C <= 8; the reference's wrapper splits C = 4 / 8 over threads, which changes nothing but the atomics' order),
+// channel pairs for half.  Atomics into the zero-initialised gradient table.  (fp32: used for small batches and the general
+// D/C/gridtype cases; large D = 4, C = 2 batches take the tiled kernel below.)
+template <typename T, uint32_t D, uint32_t C>
 __global__ __launch_bounds__(256) void grid_backward_kernel(
-    const float *__restrict__ grad, const float *__restrict__ inputs,
-    const int32_t *__restrict__ offsets, float *__restrict__ grad_grid, uint32_t B, uint32_t L,
+    const T *__restrict__ grad, const float *__restrict__ inputs,
+    const int32_t *__restrict__ offsets, T *__restrict__ grad_grid, uint32_t B, uint32_t L,
     GridLevels lv, uint32_t gridtype, bool align_corners, uint32_t interp) {
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    using M = GridMath<T>;
+    constexpr uint32_t K = M::per_thread(C);
+    static_assert(C % K == 0, "a thread's channels must divide C");
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t b = t / (C / K), ch = (t - b * (C / K)) * K;
     if (b >= B) return;
     const uint32_t level = blockIdx.y;
-    float *gg = grad_grid + (size_t)(uint32_t)offsets[level] * C;
+    T *gg = grad_grid + (size_t)(uint32_t)offsets[level] * C;
     const float *x = inputs + (size_t)b * D;
-    const float *g = grad + ((size_t)level * B + b) * C;
+    const T *g = grad + ((size_t)level * B + b) * C + ch;
     const uint32_t hashmap_size = (uint32_t)(offsets[level + 1] - offsets[level]);
     const float scale = lv.scale[level];
     const uint32_t resolution = lv.resolution[level];
 
-    float pos[D];
+    float pos[D], pos_deriv[D];
     uint32_t pg[D];
 #pragma unroll
     for (uint32_t d = 0; d < D; d++) {
         const float xd = x[d];
         if (xd < 0.f || xd > 1.f) return;  // gradient stays zero
-        pos[d] = __fmaf_rn(xd, scale, align_corners ? 0.0f : 0.5f);
-        const float fl = floorf(pos[d]);
-        pg[d] = (uint32_t)fl;
-        pos[d] -= fl;
-        if (interp == 1)
-            pos[d] = __fmul_rn(__fmul_rn(pos[d], pos[d]), __fsub_rn(3.0f, __fmul_rn(2.0f, pos[d])));
+        grid_cell_axis(xd, scale, align_corners, interp, pos[d], pos_deriv[d], pg[d]);
     }
-    float gc[C];
+    T gc[K];
 #pragma unroll
-    for (uint32_t ch = 0; ch < C; ch++) gc[ch] = g[ch];
+    for (uint32_t k = 0; k < K; k++) gc[k] = g[k];
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
         float w = 1.f;
@@ -243,7 +325,7 @@ __global__ __launch_bounds__(256) void grid_backward_kernel(
         }
         const uint32_t index = grid_index<D>(gridtype, align_corners, hashmap_size, resolution, pl) * C;
 #pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) atomicAdd(&gg[index + ch], __fmul_rn(w, gc[ch]));
+        for (uint32_t k = 0; k < K; k += M::kAtomic) M::scatter(gg + index + ch + k, w, gc + k);
     }
 }
 
@@ -497,97 +579,85 @@ __global__ __launch_bounds__(1024) void grid_backward_tiled_d4c2_kernel(
 }
 
 // gridencoder.cu:343-369
-template <uint32_t D, uint32_t C>
+template <typename T, uint32_t D, uint32_t C>
 __global__ __launch_bounds__(256) void grid_input_backward_kernel(
-    const float *__restrict__ grad, const float *__restrict__ dy_dx,
-    float *__restrict__ grad_inputs, uint32_t B, uint32_t L) {
+    const T *__restrict__ grad, const T *__restrict__ dy_dx,
+    T *__restrict__ grad_inputs, uint32_t B, uint32_t L) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * D) return;
     const uint32_t b = t / D, d = t - b * D;
-    const float *dy = dy_dx + (size_t)b * L * D * C;
-    float r = 0.f;
+    const T *dy = dy_dx + (size_t)b * L * D * C;
+    T r = T(0);
     for (uint32_t l = 0; l < L; l++) {
 #pragma unroll
         for (uint32_t ch = 0; ch < C; ch++)
-            r += grad[((size_t)l * B + b) * C + ch] * dy[(l * D + d) * C + ch];
+            r = GridMath<T>::input_grad(r, grad[((size_t)l * B + b) * C + ch], dy[(l * D + d) * C + ch]);
     }
     grad_inputs[t] = r;
 }
 
-template <uint32_t D>
-int launch_forward_c(uint32_t C, const float *in, const float *emb, const int32_t *off, float *out,
-                     uint32_t B, uint32_t L, const GridLevels &lv, float *dy, uint32_t gt, bool ac,
-                     uint32_t interp, hipStream_t st) {
-    const dim3 grid((B + 255) / 256, L), block(256);
-    switch (C) {
-        case 1: hipLaunchKernelGGL((grid_forward_kernel<D, 1>), grid, block, 0, st, in, emb, off, out, B, L, lv, dy, gt, ac, interp); break;
-        case 2: hipLaunchKernelGGL((grid_forward_kernel<D, 2>), grid, block, 0, st, in, emb, off, out, B, L, lv, dy, gt, ac, interp); break;
-        case 4: hipLaunchKernelGGL((grid_forward_kernel<D, 4>), grid, block, 0, st, in, emb, off, out, B, L, lv, dy, gt, ac, interp); break;
-        case 8: hipLaunchKernelGGL((grid_forward_kernel<D, 8>), grid, block, 0, st, in, emb, off, out, B, L, lv, dy, gt, ac, interp); break;
-        default: set_error("GridEncoding: C must be 1, 2, 4, or 8."); return 1;
+// gridencoder.cu:467-500's D x C switch: f(D, C) with both as integral constants, for the supported sizes.
+template <typename F>
+int dispatch_dc(uint32_t D, uint32_t C, F &&f) {
+    auto for_c = [&](auto d) {
+        switch (C) {
+            case 1: return f(d, std::integral_constant<uint32_t, 1>());
+            case 2: return f(d, std::integral_constant<uint32_t, 2>());
+            case 4: return f(d, std::integral_constant<uint32_t, 4>());
+            case 8: return f(d, std::integral_constant<uint32_t, 8>());
+            default: set_error("GridEncoding: C must be 1, 2, 4, or 8."); return 1;
+        }
+    };
+    switch (D) {
+        case 2: return for_c(std::integral_constant<uint32_t, 2>());
+        case 3: return for_c(std::integral_constant<uint32_t, 3>());
+        case 4: return for_c(std::integral_constant<uint32_t, 4>());
+        case 5: return for_c(std::integral_constant<uint32_t, 5>());
+        default: set_error("GridEncoding: D must be 2, 3, 4, or 5."); return 1;
     }
-    return check_launch("grid_encode_forward");
-}
-
-template <uint32_t D>
-int launch_backward_c(uint32_t C, const float *grad, const float *in, const int32_t *off, float *gg,
-                      uint32_t B, uint32_t L, const GridLevels &lv, const float *dy, float *gi,
-                      uint32_t gt, bool ac, uint32_t interp, hipStream_t st) {
-    const dim3 grid((B + 255) / 256, L), block(256);
-    const dim3 grid_in((B * D + 255) / 256);
-#define OCC_BWD(CC)                                                                                   \
-    hipLaunchKernelGGL((grid_backward_kernel<D, CC>), grid, block, 0, st, grad, in, off, gg, B, L, lv, \
-                       gt, ac, interp);                                                               \
-    if (dy) hipLaunchKernelGGL((grid_input_backward_kernel<D, CC>), grid_in, block, 0, st, grad, dy, gi, B, L);
-    switch (C) {
-        case 1: OCC_BWD(1) break;
-        case 2: OCC_BWD(2) break;
-        case 4: OCC_BWD(4) break;
-        case 8: OCC_BWD(8) break;
-        default: set_error("GridEncoding: C must be 1, 2, 4, or 8."); return 1;
-    }
-#undef OCC_BWD
-    return check_launch("grid_encode_backward");
 }
 
 }  // namespace occ
 
-static int grid_forward_impl(const float *inputs, const float *embeddings, const int32_t *offsets, const int32_t *h_off,
-                             float *outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
-                             float *dy_dx, uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
+// One operator entry for the storage type T; `name` is the entry's name in its errors.  fp32 with the caller's host copy of
+// the offsets (h_off) takes the D = 4, C = 2 kernels above where they apply, everything else the generic kernels.
+template <typename T>
+static int grid_forward_impl(const char *name, const float *inputs, const T *embeddings, const int32_t *offsets,
+                             const int32_t *h_off, T *outputs, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
+                             uint32_t H, T *dy_dx, uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
     using namespace occ;
     if (B == 0) return 0;
-    OCC_REQUIRE(inputs && embeddings && offsets && outputs, "grid_encode_forward: null tensor");
-    OCC_REQUIRE(L >= 1 && L <= kMaxLevels, "grid_encode_forward: L=%u unsupported (1..%d)", L, kMaxLevels);
+    OCC_REQUIRE(inputs && embeddings && offsets && outputs, "%s: null tensor", name);
+    OCC_REQUIRE(L >= 1 && L <= kMaxLevels, "%s: L=%u unsupported (1..%d)", name, L, kMaxLevels);
     const GridLevels lv = make_grid_levels(L, S, H);
     hipStream_t st = as_stream(stream);
     const bool ac = align_corners != 0;
-    if (h_off && D == 4 && C == 2 && gridtype == 0 && !ac && interp == 0 && !dy_dx && B <= (1u << 28)) {
-        uint32_t sizes[kMaxLevels] = {0};
-        for (uint32_t l = 0; l < L; l++) sizes[l] = (uint32_t)(h_off[l + 1] - h_off[l]);
-        const GridModes4 gm = make_grid_modes_d4(L, lv, sizes);
-        // level pairs dealt to the XCDs (see the kernel): measured 1.6x faster with half the fabric fetches on large batches
-        // (profiles/r05_xcd_levels.md), same bits -- the default from 32 768 samples up (knob grid_xcd: 1 always, 2 never)
-        const int xk = knob(kKnobGridXcd);
-        if (xk == 1 || (xk == 0 && B >= 32768u)) {
-            hipLaunchKernelGGL(grid_forward_d4c2_xcd_kernel, dim3(((B + 255) / 256) * 8), dim3(256), 0, st,
+    if constexpr (std::is_same<T, float>::value) {
+        if (h_off && D == 4 && C == 2 && gridtype == 0 && !ac && interp == 0 && !dy_dx && B <= (1u << 28)) {
+            uint32_t sizes[kMaxLevels] = {0};
+            for (uint32_t l = 0; l < L; l++) sizes[l] = (uint32_t)(h_off[l + 1] - h_off[l]);
+            const GridModes4 gm = make_grid_modes_d4(L, lv, sizes);
+            // level pairs dealt to the XCDs (see the kernel): measured 1.6x faster with half the fabric fetches on large batches
+            // (profiles/r05_xcd_levels.md), same bits -- the default from 32 768 samples up (knob grid_xcd: 1 always, 2 never)
+            const int xk = knob(kKnobGridXcd);
+            if (xk == 1 || (xk == 0 && B >= 32768u)) {
+                hipLaunchKernelGGL(grid_forward_d4c2_xcd_kernel, dim3(((B + 255) / 256) * 8), dim3(256), 0, st,
+                                   reinterpret_cast<const float4 *>(inputs), reinterpret_cast<const float2 *>(embeddings), offsets,
+                                   reinterpret_cast<float2 *>(outputs), B, L, lv, gm);
+                return check_launch(name);
+            }
+            const uint32_t threads = B * 8;
+            hipLaunchKernelGGL(grid_forward_d4c2_kernel, dim3((threads + 255) / 256), dim3(256), 0, st,
                                reinterpret_cast<const float4 *>(inputs), reinterpret_cast<const float2 *>(embeddings), offsets,
                                reinterpret_cast<float2 *>(outputs), B, L, lv, gm);
-            return check_launch("grid_encode_forward");
+            return check_launch(name);
         }
-        const uint32_t threads = B * 8;
-        hipLaunchKernelGGL(grid_forward_d4c2_kernel, dim3((threads + 255) / 256), dim3(256), 0, st,
-                           reinterpret_cast<const float4 *>(inputs), reinterpret_cast<const float2 *>(embeddings), offsets,
-                           reinterpret_cast<float2 *>(outputs), B, L, lv, gm);
-        return check_launch("grid_encode_forward");
     }
-    switch (D) {
-        case 2: return launch_forward_c<2>(C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, st);
-        case 3: return launch_forward_c<3>(C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, st);
-        case 4: return launch_forward_c<4>(C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, st);
-        case 5: return launch_forward_c<5>(C, inputs, embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp, st);
-        default: set_error("GridEncoding: D must be 2, 3, 4, or 5."); return 1;
-    }
+    return dispatch_dc(D, C, [&](auto d, auto c) {
+        hipLaunchKernelGGL((grid_forward_kernel<T, d.value, c.value>), dim3((B + 255) / 256, L), dim3(256), 0, st, inputs,
+                           embeddings, offsets, outputs, B, L, lv, dy_dx, gridtype, ac, interp);
+        return check_launch(name);
+    });
 }
 
 OCC_API int occnerf_grid_encode_forward(const float *inputs, const float *embeddings,
@@ -595,8 +665,8 @@ OCC_API int occnerf_grid_encode_forward(const float *inputs, const float *embedd
                                         uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
                                         float *dy_dx, uint32_t gridtype, int align_corners,
                                         uint32_t interp, void *stream) {
-    return grid_forward_impl(inputs, embeddings, offsets, nullptr, outputs, B, D, C, L, S, H, dy_dx, gridtype, align_corners,
-                             interp, stream);
+    return grid_forward_impl("grid_encode_forward", inputs, embeddings, offsets, nullptr, outputs, B, D, C, L, S, H, dy_dx,
+                             gridtype, align_corners, interp, stream);
 }
 
 OCC_API int occnerf_grid_encode_forward_h(const float *inputs, const float *embeddings, const int32_t *offsets,
@@ -604,73 +674,99 @@ OCC_API int occnerf_grid_encode_forward_h(const float *inputs, const float *embe
                                           uint32_t L, float S, uint32_t H, float *dy_dx, uint32_t gridtype,
                                           int align_corners, uint32_t interp, void *stream) {
     OCC_REQUIRE(h_offsets, "grid_encode_forward_h: null host offsets");
-    return grid_forward_impl(inputs, embeddings, offsets, h_offsets, outputs, B, D, C, L, S, H, dy_dx, gridtype,
+    return grid_forward_impl("grid_encode_forward", inputs, embeddings, offsets, h_offsets, outputs, B, D, C, L, S, H, dy_dx,
+                             gridtype, align_corners, interp, stream);
+}
+
+OCC_API int occnerf_grid_encode_forward_f16(const float *inputs, const void *embeddings, const int32_t *offsets, void *outputs,
+                                            uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void *dy_dx,
+                                            uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
+    using occ::half_t;
+    return grid_forward_impl("grid_encode_forward_f16", inputs, static_cast<const half_t *>(embeddings), offsets, nullptr,
+                             static_cast<half_t *>(outputs), B, D, C, L, S, H, static_cast<half_t *>(dy_dx), gridtype,
                              align_corners, interp, stream);
 }
 
-static int grid_backward_impl(const float *grad, const float *inputs, const int32_t *offsets, const int32_t *h_off,
-                              float *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S,
-                              uint32_t H, const float *dy_dx, float *grad_inputs, uint32_t gridtype,
-                              int align_corners, uint32_t interp, void *scratch, int64_t scratch_bytes, void *stream) {
+OCC_API int occnerf_grid_encode_forward_f64(const float *inputs, const double *embeddings, const int32_t *offsets, double *outputs,
+                                            uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, double *dy_dx,
+                                            uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
+    return grid_forward_impl("grid_encode_forward_f64", inputs, embeddings, offsets, nullptr, outputs, B, D, C, L, S, H, dy_dx,
+                             gridtype, align_corners, interp, stream);
+}
+
+template <typename T>
+static int grid_backward_impl(const char *name, const T *grad, const float *inputs, const int32_t *offsets,
+                              const int32_t *h_off, T *grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L,
+                              float S, uint32_t H, const T *dy_dx, T *grad_inputs, uint32_t gridtype, int align_corners,
+                              uint32_t interp, void *scratch, int64_t scratch_bytes, void *stream) {
     using namespace occ;
     if (B == 0) return 0;
-    OCC_REQUIRE(grad && inputs && offsets && grad_embeddings, "grid_encode_backward: null tensor");
-    OCC_REQUIRE((dy_dx == nullptr) == (grad_inputs == nullptr),
-                "grid_encode_backward: dy_dx and grad_inputs must be given together");
-    OCC_REQUIRE(L >= 1 && L <= kMaxLevels, "grid_encode_backward: L=%u unsupported", L);
+    OCC_REQUIRE(grad && inputs && offsets && grad_embeddings, "%s: null tensor", name);
+    OCC_REQUIRE((dy_dx == nullptr) == (grad_inputs == nullptr), "%s: dy_dx and grad_inputs must be given together", name);
+    OCC_REQUIRE(L >= 1 && L <= kMaxLevels, "%s: L=%u unsupported", name, L);
     const GridLevels lv = make_grid_levels(L, S, H);
     hipStream_t st = as_stream(stream);
     const bool ac = align_corners != 0;
-    if (h_off && D == 4 && C == 2 && gridtype == 0 && !ac && interp == 0 && B >= 32768) {
-        // tiled, atomics-free path; the level sizes come from the caller's HOST copy of the offsets
-        // Jobs = (level, tile, sample slice).  The encoder's inputs are anything but uniform -- a point projected onto the
-        // body surface plus a clamped distance: 87 % of the samples have their level-0 base corner in ONE of its 11 tiles,
-        // and on every hashed level some tile holds a few hot cells -- so per-job times measured with wall_clock64 ranged
-        // from 0.1 ms to 3.5 ms on a hashed level and 13.5 ms on level 0, and the kernel lasted as long as its hottest
-        // tile (whose lanes also serialise on same-address LDS atomics).  Tiles are therefore split over sample slices:
-        // 16 per tile on dense levels, 8 on hashed ones (32 / 16 measured slower: more partial tiles to merge).  A slice
-        // scans only its share of the tile-set masks, so the total scan work is unchanged; partial tiles meet in the
-        // table through fp32 atomics on their non-zero entries, which are few because the hot cells are few.
-        TileJobs jobs;
-        uint32_t sizes[kMaxLevels] = {0};
-        for (uint32_t l = 0; l < L; l++) sizes[l] = (uint32_t)(h_off[l + 1] - h_off[l]);
-        jobs.modes = make_grid_modes_d4(L, lv, sizes);
-        uint32_t total = 0;
-        for (uint32_t l = 0; l < (uint32_t)kMaxLevels; l++) {
-            jobs.first_block[l] = total;
-            jobs.nslices[l] = 1;
-            if (l >= L) continue;
-            const uint32_t nt = (sizes[l] + kTileEntries - 1) / kTileEntries;
-            jobs.nslices[l] = jobs.modes.mode[l] == kGridDense ? 16u : 8u;
-            total += nt * jobs.nslices[l];
-        }
-        jobs.first_block[kMaxLevels] = total;
-        const bool fits = total > 0 && total < 65536;
-        if (fits) {
-            // with L * B * 8 bytes of scratch from the caller: tile-set pre-pass + masked, compacted scan
-            bool max64 = true;
-            for (uint32_t l = 0; l < L; l++) max64 = max64 && (sizes[l] + kTileEntries - 1) / kTileEntries <= 64;
-            unsigned long long *masks = nullptr;
-            if (scratch && max64 && scratch_bytes >= (int64_t)L * B * 8) {
-                masks = reinterpret_cast<unsigned long long *>(scratch);
-                hipLaunchKernelGGL(grid_tile_mask_kernel, dim3((B + 255) / 256, L), dim3(256), 0, st, grad,
-                                   reinterpret_cast<const float4 *>(inputs), offsets, B, lv, jobs.modes, masks);
+    if constexpr (std::is_same<T, float>::value) {
+        if (h_off && D == 4 && C == 2 && gridtype == 0 && !ac && interp == 0 && B >= 32768) {
+            // tiled, atomics-free path; the level sizes come from the caller's HOST copy of the offsets
+            // Jobs = (level, tile, sample slice).  The encoder's inputs are anything but uniform -- a point projected onto the
+            // body surface plus a clamped distance: 87 % of the samples have their level-0 base corner in ONE of its 11 tiles,
+            // and on every hashed level some tile holds a few hot cells -- so per-job times measured with wall_clock64 ranged
+            // from 0.1 ms to 3.5 ms on a hashed level and 13.5 ms on level 0, and the kernel lasted as long as its hottest
+            // tile (whose lanes also serialise on same-address LDS atomics).  Tiles are therefore split over sample slices:
+            // 16 per tile on dense levels, 8 on hashed ones (32 / 16 measured slower: more partial tiles to merge).  A slice
+            // scans only its share of the tile-set masks, so the total scan work is unchanged; partial tiles meet in the
+            // table through fp32 atomics on their non-zero entries, which are few because the hot cells are few.
+            TileJobs jobs;
+            uint32_t sizes[kMaxLevels] = {0};
+            for (uint32_t l = 0; l < L; l++) sizes[l] = (uint32_t)(h_off[l + 1] - h_off[l]);
+            jobs.modes = make_grid_modes_d4(L, lv, sizes);
+            uint32_t total = 0;
+            for (uint32_t l = 0; l < (uint32_t)kMaxLevels; l++) {
+                jobs.first_block[l] = total;
+                jobs.nslices[l] = 1;
+                if (l >= L) continue;
+                const uint32_t nt = (sizes[l] + kTileEntries - 1) / kTileEntries;
+                jobs.nslices[l] = jobs.modes.mode[l] == kGridDense ? 16u : 8u;
+                total += nt * jobs.nslices[l];
             }
-            hipLaunchKernelGGL(grid_backward_tiled_d4c2_kernel, dim3(total), dim3(1024), 0, st, grad,
-                               reinterpret_cast<const float4 *>(inputs), offsets, grad_embeddings, B, lv, jobs, masks);
-            if (dy_dx)
-                hipLaunchKernelGGL((grid_input_backward_kernel<4, 2>), dim3((B * 4 + 255) / 256), dim3(256), 0, st, grad,
-                                   dy_dx, grad_inputs, B, L);
-            return check_launch("grid_encode_backward");
+            jobs.first_block[kMaxLevels] = total;
+            const bool fits = total > 0 && total < 65536;
+            if (fits) {
+                // with L * B * 8 bytes of scratch from the caller: tile-set pre-pass + masked, compacted scan
+                bool max64 = true;
+                for (uint32_t l = 0; l < L; l++) max64 = max64 && (sizes[l] + kTileEntries - 1) / kTileEntries <= 64;
+                unsigned long long *masks = nullptr;
+                if (scratch && max64 && scratch_bytes >= (int64_t)L * B * 8) {
+                    masks = reinterpret_cast<unsigned long long *>(scratch);
+                    hipLaunchKernelGGL(grid_tile_mask_kernel, dim3((B + 255) / 256, L), dim3(256), 0, st, grad,
+                                       reinterpret_cast<const float4 *>(inputs), offsets, B, lv, jobs.modes, masks);
+                }
+                hipLaunchKernelGGL(grid_backward_tiled_d4c2_kernel, dim3(total), dim3(1024), 0, st, grad,
+                                   reinterpret_cast<const float4 *>(inputs), offsets, grad_embeddings, B, lv, jobs, masks);
+                if (dy_dx)
+                    hipLaunchKernelGGL((grid_input_backward_kernel<float, 4, 2>), dim3((B * 4 + 255) / 256), dim3(256), 0, st, grad,
+                                       dy_dx, grad_inputs, B, L);
+                return check_launch(name);
+            }
         }
     }
-    switch (D) {
-        case 2: return launch_backward_c<2>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, st);
-        case 3: return launch_backward_c<3>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, st);
-        case 4: return launch_backward_c<4>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, st);
-        case 5: return launch_backward_c<5>(C, grad, inputs, offsets, grad_embeddings, B, L, lv, dy_dx, grad_inputs, gridtype, ac, interp, st);
-        default: set_error("GridEncoding: D must be 2, 3, 4, or 5."); return 1;
-    }
+    return dispatch_dc(D, C, [&](auto d, auto c) {
+        constexpr uint32_t K = GridMath<T>::per_thread(c.value);
+        if constexpr (c.value % K != 0) {
+            set_error("%s: C = %u has no packed-half atomic (the reference's at::Half atomicAdd is an empty stub, "
+                      "gridencoder.cu:22-26; grid.py:44 keeps float embeddings when C is odd)", name, c.value);
+            return 1;
+        } else {
+            hipLaunchKernelGGL((grid_backward_kernel<T, d.value, c.value>), dim3((B * (c.value / K) + 255) / 256, L), dim3(256),
+                               0, st, grad, inputs, offsets, grad_embeddings, B, L, lv, gridtype, ac, interp);
+            if (dy_dx)
+                hipLaunchKernelGGL((grid_input_backward_kernel<T, d.value, c.value>), dim3((B * d.value + 255) / 256), dim3(256),
+                                   0, st, grad, dy_dx, grad_inputs, B, L);
+            return check_launch(name);
+        }
+    });
 }
 
 namespace occ {
@@ -797,8 +893,8 @@ OCC_API int occnerf_grid_encode_backward(const float *grad, const float *inputs,
                                          float *grad_inputs, uint32_t gridtype, int align_corners, uint32_t interp,
                                          void *stream) {
     (void)embeddings;
-    return grid_backward_impl(grad, inputs, offsets, nullptr, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
-                              gridtype, align_corners, interp, nullptr, 0, stream);
+    return grid_backward_impl("grid_encode_backward", grad, inputs, offsets, nullptr, grad_embeddings, B, D, C, L, S, H, dy_dx,
+                              grad_inputs, gridtype, align_corners, interp, nullptr, 0, stream);
 }
 
 OCC_API int occnerf_grid_encode_backward_h(const float *grad, const float *inputs, const float *embeddings,
@@ -809,8 +905,28 @@ OCC_API int occnerf_grid_encode_backward_h(const float *grad, const float *input
                                            void *stream) {
     (void)embeddings;
     OCC_REQUIRE(h_offsets, "grid_encode_backward_h: null host offsets");
-    return grid_backward_impl(grad, inputs, offsets, h_offsets, grad_embeddings, B, D, C, L, S, H, dy_dx, grad_inputs,
-                              gridtype, align_corners, interp, scratch, scratch_bytes, stream);
+    return grid_backward_impl("grid_encode_backward", grad, inputs, offsets, h_offsets, grad_embeddings, B, D, C, L, S, H,
+                              dy_dx, grad_inputs, gridtype, align_corners, interp, scratch, scratch_bytes, stream);
+}
+
+OCC_API int occnerf_grid_encode_backward_f16(const void *grad, const float *inputs, const void *embeddings,
+                                             const int32_t *offsets, void *grad_embeddings, uint32_t B, uint32_t D, uint32_t C,
+                                             uint32_t L, float S, uint32_t H, const void *dy_dx, void *grad_inputs,
+                                             uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
+    using occ::half_t;
+    (void)embeddings;
+    return grid_backward_impl("grid_encode_backward_f16", static_cast<const half_t *>(grad), inputs, offsets, nullptr,
+                              static_cast<half_t *>(grad_embeddings), B, D, C, L, S, H, static_cast<const half_t *>(dy_dx),
+                              static_cast<half_t *>(grad_inputs), gridtype, align_corners, interp, nullptr, 0, stream);
+}
+
+OCC_API int occnerf_grid_encode_backward_f64(const double *grad, const float *inputs, const double *embeddings,
+                                             const int32_t *offsets, double *grad_embeddings, uint32_t B, uint32_t D, uint32_t C,
+                                             uint32_t L, float S, uint32_t H, const double *dy_dx, double *grad_inputs,
+                                             uint32_t gridtype, int align_corners, uint32_t interp, void *stream) {
+    (void)embeddings;
+    return grid_backward_impl("grid_encode_backward_f64", grad, inputs, offsets, nullptr, grad_embeddings, B, D, C, L, S, H,
+                              dy_dx, grad_inputs, gridtype, align_corners, interp, nullptr, 0, stream);
 }
 
 OCC_API int occnerf_grad_total_variation(const float *, const float *, float *, const int32_t *,

@@ -108,10 +108,14 @@ def _ptr_table(tensors, name):
 # ------------------------------------------------------------------ grid encoder (section 1)
 def _encoder_dtype(t, what):
     """gridencoder.cu:467,500 dispatch on the tensor dtype over float / double / half (grid.py:42-45 feeds half embeddings
-    under autocast): all three cases of AT_DISPATCH_FLOATING_TYPES_AND_HALF are built (csrc/grid_encode{,_f16,_f64}.hip)."""
+    under autocast): all three cases of AT_DISPATCH_FLOATING_TYPES_AND_HALF are built (csrc/grid_encode.hip)."""
     if t.dtype not in (torch.float32, torch.float16, torch.float64):
         raise RuntimeError(f'{what}: tensors are {t.dtype}; gridencoder.cu:467 dispatches float32, float64 and float16')
     return t.dtype
+
+
+# entry-point suffix per dtype; fp32 takes the `_h` entries, which also get the host copy of the offsets
+_ENCODER_ENTRY = {torch.float32: '_h', torch.float16: '_f16', torch.float64: '_f64'}
 
 
 def grid_grad_runs(grad_rows, inputs, B, D, L, Cc):
@@ -129,25 +133,14 @@ def grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, Cc, L, S, H,
     """Same positional signature as the reference's `_gridencoder.grid_encode_forward`
     (bindings.cpp:6); writes `outputs[L,B,C]` (and `dy_dx`) in place.  Dispatches on embeddings.dtype like the reference."""
     dt = _encoder_dtype(embeddings, 'grid_encode_forward')
+    fp32 = dt == torch.float32
     with _guard(inputs):
-        if dt == torch.float64:
-            rc = _lib.lib().occnerf_grid_encode_forward_f64(
-                _chk(inputs, torch.float32, 'inputs'), _chk(embeddings, torch.float64, 'embeddings'),
-                _chk(offsets, torch.int32, 'offsets'), _chk(outputs, torch.float64, 'outputs'),
-                int(B), int(D), int(Cc), int(L), float(S), int(H), _opt(dy_dx, torch.float64, 'dy_dx'),
-                int(gridtype), int(bool(align_corners)), int(interp), _stream(inputs))
-        elif dt == torch.float16:
-            rc = _lib.lib().occnerf_grid_encode_forward_f16(
-                _chk(inputs, torch.float32, 'inputs'), _chk(embeddings, torch.float16, 'embeddings'),
-                _chk(offsets, torch.int32, 'offsets'), _chk(outputs, torch.float16, 'outputs'),
-                int(B), int(D), int(Cc), int(L), float(S), int(H), _opt(dy_dx, torch.float16, 'dy_dx'),
-                int(gridtype), int(bool(align_corners)), int(interp), _stream(inputs))
-        else:
-            rc = _lib.lib().occnerf_grid_encode_forward_h(
-                _chk(inputs, torch.float32, 'inputs'), _chk(embeddings, torch.float32, 'embeddings'),
-                _chk(offsets, torch.int32, 'offsets'), _host_offsets(offsets), _chk(outputs, torch.float32, 'outputs'),
-                int(B), int(D), int(Cc), int(L), float(S), int(H), _opt(dy_dx, torch.float32, 'dy_dx'),
-                int(gridtype), int(bool(align_corners)), int(interp), _stream(inputs))
+        args = [_chk(inputs, torch.float32, 'inputs'), _chk(embeddings, dt, 'embeddings'), _chk(offsets, torch.int32, 'offsets')]
+        if fp32:
+            args.append(_host_offsets(offsets))
+        rc = getattr(_lib.lib(), 'occnerf_grid_encode_forward' + _ENCODER_ENTRY[dt])(
+            *args, _chk(outputs, dt, 'outputs'), int(B), int(D), int(Cc), int(L), float(S), int(H), _opt(dy_dx, dt, 'dy_dx'),
+            int(gridtype), int(bool(align_corners)), int(interp), _stream(inputs))
     _lib.check(rc, 'grid_encode_forward')
 
 
@@ -155,38 +148,21 @@ def grid_encode_backward(grad, inputs, embeddings, offsets, grad_embeddings, B, 
                          dy_dx=None, grad_inputs=None, gridtype=0, align_corners=False, interp=0):
     """`_gridencoder.grid_encode_backward` (bindings.cpp:7); dispatches on grad.dtype like the reference (:500)."""
     dt = _encoder_dtype(grad, 'grid_encode_backward')
-    if dt == torch.float64:
-        with _guard(inputs):
-            rc = _lib.lib().occnerf_grid_encode_backward_f64(
-                _chk(grad, torch.float64, 'grad'), _chk(inputs, torch.float32, 'inputs'),
-                _chk(embeddings, torch.float64, 'embeddings'), _chk(offsets, torch.int32, 'offsets'),
-                _chk(grad_embeddings, torch.float64, 'grad_embeddings'), int(B), int(D), int(Cc), int(L), float(S), int(H),
-                _opt(dy_dx, torch.float64, 'dy_dx'), _opt(grad_inputs, torch.float64, 'grad_inputs'), int(gridtype),
-                int(bool(align_corners)), int(interp), _stream(inputs))
-        _lib.check(rc, 'grid_encode_backward')
-        return
-    if dt == torch.float16:
-        with _guard(inputs):
-            rc = _lib.lib().occnerf_grid_encode_backward_f16(
-                _chk(grad, torch.float16, 'grad'), _chk(inputs, torch.float32, 'inputs'),
-                _chk(embeddings, torch.float16, 'embeddings'), _chk(offsets, torch.int32, 'offsets'),
-                _chk(grad_embeddings, torch.float16, 'grad_embeddings'), int(B), int(D), int(Cc), int(L), float(S), int(H),
-                _opt(dy_dx, torch.float16, 'dy_dx'), _opt(grad_inputs, torch.float16, 'grad_inputs'), int(gridtype),
-                int(bool(align_corners)), int(interp), _stream(inputs))
-        _lib.check(rc, 'grid_encode_backward')
-        return
+    fp32 = dt == torch.float32
     # room for the tile-set pre-pass of the tiled backward (large D = 4, C = 2 batches only)
-    scratch = torch.empty(int(L) * int(B), device=inputs.device, dtype=torch.int64) if (int(D) == 4 and int(Cc) == 2
+    scratch = torch.empty(int(L) * int(B), device=inputs.device, dtype=torch.int64) if (fp32 and int(D) == 4 and int(Cc) == 2
                                                                                       and int(B) >= 32768) else None
     with _guard(inputs):
-        rc = _lib.lib().occnerf_grid_encode_backward_h(
-            _chk(grad, torch.float32, 'grad'), _chk(inputs, torch.float32, 'inputs'),
-            _chk(embeddings, torch.float32, 'embeddings'), _chk(offsets, torch.int32, 'offsets'),
-            _host_offsets(offsets), _chk(grad_embeddings, torch.float32, 'grad_embeddings'), int(B), int(D), int(Cc),
-            int(L), float(S), int(H), _opt(dy_dx, torch.float32, 'dy_dx'),
-            _opt(grad_inputs, torch.float32, 'grad_inputs'), int(gridtype),
-            int(bool(align_corners)), int(interp), None if scratch is None else scratch.data_ptr(),
-            0 if scratch is None else scratch.numel() * 8, _stream(inputs))
+        args = [_chk(grad, dt, 'grad'), _chk(inputs, torch.float32, 'inputs'), _chk(embeddings, dt, 'embeddings'),
+                _chk(offsets, torch.int32, 'offsets')]
+        if fp32:
+            args.append(_host_offsets(offsets))
+        args += [_chk(grad_embeddings, dt, 'grad_embeddings'), int(B), int(D), int(Cc), int(L), float(S), int(H),
+                 _opt(dy_dx, dt, 'dy_dx'), _opt(grad_inputs, dt, 'grad_inputs'), int(gridtype), int(bool(align_corners)),
+                 int(interp)]
+        if fp32:
+            args += [None if scratch is None else scratch.data_ptr(), 0 if scratch is None else scratch.numel() * 8]
+        rc = getattr(_lib.lib(), 'occnerf_grid_encode_backward' + _ENCODER_ENTRY[dt])(*args, _stream(inputs))
     _lib.check(rc, 'grid_encode_backward')
 
 
