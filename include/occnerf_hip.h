@@ -652,6 +652,30 @@ int occnerf_patch_assemble(const float *rgb, const int32_t *row_of_pix, int64_t 
                            const float *h_bgcolor01, float *img, void *stream);
 int occnerf_patch_assemble_backward(const float *d_img, const int32_t *pix_of_row, int64_t R, float *d_rgb, void *stream);
 
+/* The training batch of one prepared dataset frame, built on the device: core/data/occnerf/train.py:167-273
+ * (get_patch_ray_indices, _get_patch_ray_indices), :322-348 (sample_patch_rays) and the blend of :296-297 + :398.
+ * Inputs: image[H,W,3], alpha[H,W,3] uint8 (the frame's PNGs, resident; the occlusion band of :286-287 already applied to
+ * alpha), rays8[H*W,8] and box_mask[H*W] as occnerf_gen_rays wrote them.  HOST: h_u[n_patches,2] doubles in [0, 1),
+ * subject_ratio = cfg.patch.sample_subject_ratio, h_bgcolor[3] in 0..255.
+ * Per patch: u0 < subject_ratio picks the subject class (alpha channel 0 > 0, :470), otherwise box-and-not-subject
+ * (:179-182); an EMPTY class falls back to the other one (the reference would raise inside np.random.choice), both empty puts
+ * the centre at pixel (0, 0).  The centre is the k-th pixel of the class in row-major order, k = min(floor(u1 * count),
+ * count - 1) (np.where's order, :236-242); x_min = clip(cx - size / 2, 0, W - size), y likewise (:245-253).
+ * Rows: the patch pixels whose ray hits the box, row-major inside a patch, patches in draw order (:262-273, :214); a pixel
+ * inside two overlapping patches gives two rows.  R = the row count <= n_patches * size^2 =: Rmax, which every buffer is sized
+ * for.  Outputs: rays[2,Rmax,3], near[Rmax], far[Rmax], target_rgbs[Rmax,3] (rows >= R untouched), target_patches[N,S,S,3]
+ * (EVERY pixel blended, :338-343), patch_masks[N,S,S] bytes 0/1, patch_div_indices[N+1], xy_min[N,2] (x, y),
+ * pix_of_row[Rmax] = patch * S^2 + y * S + x, row_of_pix[N*S*S] (-1: no ray), n_rows[1] = R.  row_counts[2*H] is scratch.
+ * The blend runs in float64 with one rounding per operator, ((a / 255.) * image + (1.0 - a / 255.) * bgcolor) / 255. ->
+ * float32, equal to numpy's bit for bit.  Three launches, no atomics, no host wait; size <= 32 is one pass of 1 024 pixels
+ * through a 256-thread workgroup per patch (wave64 ballots, one LDS scan across the waves), larger sizes loop. */
+int32_t occnerf_patch_batch_max_patches(void);
+int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask, int32_t H,
+                        int32_t W, int32_t n_patches, int32_t size, const double *h_u, double subject_ratio,
+                        const float *h_bgcolor, int32_t *row_counts, float *rays, float *near, float *far, float *target_rgbs,
+                        float *target_patches, uint8_t *patch_masks, int32_t *patch_div_indices, int32_t *xy_min,
+                        int32_t *pix_of_row, int32_t *row_of_pix, int32_t *n_rows, void *stream);
+
 /* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
  * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
  * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance

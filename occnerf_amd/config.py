@@ -86,7 +86,16 @@ _DEFAULTS = {
     'N_samples': 128, 'perturb': 1.0, 'netchunk_per_gpu': 300000, 'chunk': 32768, 'n_gpus': 1,
     'bgcolor': [0.0, 0.0, 0.0], 'resize_img_scale': 0.5, 'show_alpha': False, 'show_truth': False,
     'patch': {'sample_subject_ratio': 0.8, 'N_patches': 6, 'size': 32},
-    'freeview': {'frame_idx': 0}, 'tpose': {}, 'movement': {}, 'train': {},
+    'freeview': {'frame_idx': 0}, 'tpose': {}, 'movement': {},
+    # train.dataset_path: a prepared dataset directory (occnerf_amd/dataset.py) -- train.py then trains on it and `movement` /
+    # `progress` read it; None: the synthetic subject.  train.images_prescaled: with resize_img_scale != 1, the PNGs are
+    # already at the training size (only K is scaled; nothing is resized here)
+    # train.seed: the loader's host RNG (frame order, patch draws, background colours); train.prefetch: build batch t+1 on a
+    # side stream while step t runs
+    'train': {'dataset_path': None, 'images_prescaled': False, 'seed': 0, 'prefetch': True},
+    # the simulated occlusion of the reference's training set (core/data/occnerf/train.py:286-287): the mask columns
+    # [mid - width // 2, mid + width // 2) of the first `range` frames of the frame list are zeroed
+    'occlude': False, 'occlusion': {'range': 405, 'mid': 451, 'width': 86},
     # eval.py: `eval.lpips True` adds an LPIPS column (weights: the LPIPS model_path / vgg16_path, else the seeded trunk)
     'eval': {'lpips': False, 'lpips_model_path': None, 'lpips_vgg16_path': None},
     # build-specific keys

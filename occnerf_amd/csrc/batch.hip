@@ -1,0 +1,279 @@
+// The training batch of a prepared dataset frame, built on the device (reference core/data/occnerf/train.py:167-273
+// get_patch_ray_indices / _get_patch_ray_indices, :322-348 sample_patch_rays, :296-297 + :398 the blend).  The frame's image
+// and mask stay resident as uint8; occnerf_gen_rays has written the ray of every pixel and the box mask.  Three launches:
+//   1. classify   one workgroup per image row: how many pixels of the row are subject (mask channel 0 > 0, train.py:470)
+//                 and how many are off-subject (box hit and not subject, :179-182);
+//   2. pick       one workgroup per patch: the class from u0, the k-th set pixel of the class in row-major order
+//                 (np.where's order, :236-242) from u1 by a scan over the row counts and a scan inside the row, then the
+//                 clipped top-left corner (:245-253).  Integer work only;
+//   3. gather     one workgroup per patch: ordered compaction of the patch pixels whose ray hits the box (wave64 ballots
+//                 and popcounts, one LDS scan across the waves, chunks of 256 pixels so any patch size loops), the rows'
+//                 rays / near / far / target colour, the whole patch's blended target, its mask and the two row <-> pixel
+//                 maps.  A patch's first row is the number of box pixels of the patches before it, which every workgroup
+//                 recounts (at most N * S * S byte loads) instead of waiting for its neighbours.
+// No atomics, no host wait; every output is a pure function of the inputs.
+//
+// The blend is the reference's float64 expression, one rounding per operator (the tree is built with -ffp-contract=off):
+//   ((m / 255.) * image + (1.0 - m / 255.) * bgcolor) / 255.  -> float32.
+#include "common.h"
+
+namespace occ {
+
+constexpr int kBatchThreads = 256;
+constexpr int kBatchWaves = kBatchThreads / kWave;
+constexpr int kMaxPatches = 64;
+
+struct PatchDraws {
+    double u[kMaxPatches][2];
+};
+
+__device__ __forceinline__ int lane_prefix(unsigned long long ballot) {      // set bits of the lanes below this one
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+}
+
+// Sum over the workgroup of a per-thread flag count; every thread gets the total.  `red` holds kBatchWaves ints.
+__device__ __forceinline__ int block_sum(int v, int *red) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();                                   // red may still be read from the previous use
+    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
+    __syncthreads();
+    int s = 0;
+#pragma unroll
+    for (int w = 0; w < kBatchWaves; w++) s += red[w];
+    return s;
+}
+
+// Exclusive prefix of `v` in thread order and the workgroup total.
+__device__ __forceinline__ int block_excl_scan(int v, int *red, int &total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == kWave - 1) red[wave] = inc;
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < kBatchWaves; w++) {
+        if (w < wave) before += red[w];
+        all += red[w];
+    }
+    total = all;
+    return before + inc - v;
+}
+
+// class 0: subject, class 1: box and not subject
+__device__ __forceinline__ bool in_class(const uint8_t *__restrict__ alpha, const uint8_t *__restrict__ box, int p, int cls) {
+    const bool subject = alpha[(size_t)p * 3] > 0;
+    return cls == 0 ? subject : (box[p] != 0 && !subject);
+}
+
+__global__ __launch_bounds__(kBatchThreads) void batch_classify_kernel(const uint8_t *__restrict__ alpha,
+                                                                      const uint8_t *__restrict__ box, int H, int W,
+                                                                      int32_t *__restrict__ row_counts) {
+    __shared__ int red[kBatchWaves];
+    const int row = blockIdx.x;
+    int n0 = 0, n1 = 0;
+    for (int x0 = 0; x0 < W; x0 += kBatchThreads) {
+        const int x = x0 + threadIdx.x;
+        bool s = false, o = false;
+        if (x < W) {
+            const int p = row * W + x;
+            s = alpha[(size_t)p * 3] > 0;
+            o = box[p] != 0 && !s;
+        }
+        n0 += __popcll(__ballot(s));                   // wave-uniform
+        n1 += __popcll(__ballot(o));
+    }
+    const bool lead = (threadIdx.x & (kWave - 1)) == 0;
+    const int t0 = block_sum(lead ? n0 : 0, red);
+    const int t1 = block_sum(lead ? n1 : 0, red);
+    if (threadIdx.x == 0) {
+        row_counts[row] = t0;
+        row_counts[H + row] = t1;
+    }
+}
+
+__global__ __launch_bounds__(kBatchThreads) void batch_pick_kernel(const uint8_t *__restrict__ alpha,
+                                                                  const uint8_t *__restrict__ box, int H, int W, int size,
+                                                                  PatchDraws draws, double subject_ratio,
+                                                                  const int32_t *__restrict__ row_counts,
+                                                                  int32_t *__restrict__ xy_min) {
+    __shared__ int red[kBatchWaves];
+    __shared__ int found[2];                           // row, index inside the row; then centre x
+    const int patch = blockIdx.x, t = threadIdx.x;
+    const int per = (H + kBatchThreads - 1) / kBatchThreads;
+    const int r0 = min(t * per, H), r1 = min(r0 + per, H);
+    int s0 = 0, s1 = 0;
+    for (int r = r0; r < r1; r++) {
+        s0 += row_counts[r];
+        s1 += row_counts[H + r];
+    }
+    int total0, total1;
+    const int e0 = block_excl_scan(s0, red, total0);
+    const int e1 = block_excl_scan(s1, red, total1);
+    int cls = draws.u[patch][0] < subject_ratio ? 0 : 1;                 // train.py:195
+    if ((cls == 0 ? total0 : total1) == 0) cls ^= 1;                     // empty class: the other one (documented fallback)
+    const int count = cls == 0 ? total0 : total1;
+    int cx = 0, cy = 0;
+    if (count > 0) {                                                     // wave- and block-uniform
+        long long k = (long long)floor(draws.u[patch][1] * (double)count);
+        k = k < 0 ? 0 : (k > count - 1 ? count - 1 : k);
+        const int excl = cls == 0 ? e0 : e1, mine = cls == 0 ? s0 : s1;
+        if (k >= excl && k < excl + mine) {                              // exactly one thread
+            int rem = (int)k - excl;
+            for (int r = r0; r < r1; r++) {
+                const int c = row_counts[cls * H + r];
+                if (rem < c) {
+                    found[0] = r;
+                    found[1] = rem;
+                    break;
+                }
+                rem -= c;
+            }
+        }
+        __syncthreads();
+        cy = found[0];
+        const int rem_row = found[1];
+        const int perw = (W + kBatchThreads - 1) / kBatchThreads;
+        const int x0 = min(t * perw, W), x1 = min(x0 + perw, W);
+        int sw = 0;
+        for (int x = x0; x < x1; x++) sw += in_class(alpha, box, cy * W + x, cls) ? 1 : 0;
+        int totalw;
+        const int ew = block_excl_scan(sw, red, totalw);
+        if (rem_row >= ew && rem_row < ew + sw) {
+            int rem = rem_row - ew;
+            for (int x = x0; x < x1; x++) {
+                if (in_class(alpha, box, cy * W + x, cls)) {
+                    if (rem == 0) {
+                        found[0] = x;
+                        break;
+                    }
+                    rem--;
+                }
+            }
+        }
+        __syncthreads();
+        cx = found[0];
+    }
+    if (t == 0) {
+        const int half = size / 2;                                       // train.py:245-253
+        xy_min[patch * 2 + 0] = min(max(cx - half, 0), W - size);
+        xy_min[patch * 2 + 1] = min(max(cy - half, 0), H - size);
+    }
+}
+
+struct BatchOut {
+    float *rays, *near, *far, *target_rgbs, *target_patches;
+    uint8_t *patch_masks;
+    int32_t *patch_div_indices, *pix_of_row, *row_of_pix, *n_rows;
+};
+
+__global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8_t *__restrict__ image,
+                                                                    const uint8_t *__restrict__ alpha,
+                                                                    const float *__restrict__ rays8,
+                                                                    const uint8_t *__restrict__ box, int W, int n_patches,
+                                                                    int size, double bg0, double bg1, double bg2,
+                                                                    const int32_t *__restrict__ xy_min, BatchOut out) {
+    __shared__ int red[kBatchWaves];
+    const int patch = blockIdx.x, t = threadIdx.x;
+    const int npix = size * size;
+    const int64_t rmax = (int64_t)n_patches * npix;
+    // first row of this patch: the box pixels of the patches drawn before it
+    int before = 0;
+    for (int q = 0; q < patch; q++) {
+        const int qx = xy_min[q * 2], qy = xy_min[q * 2 + 1];
+        for (int i = t; i < npix; i += kBatchThreads) before += box[(qy + i / size) * W + qx + i % size] != 0 ? 1 : 0;
+    }
+    int base = block_sum(before, red);
+    if (t == 0) out.patch_div_indices[patch] = base;
+    const int x_min = xy_min[patch * 2], y_min = xy_min[patch * 2 + 1];
+    const double bg[3] = {bg0, bg1, bg2};
+    for (int i0 = 0; i0 < npix; i0 += kBatchThreads) {
+        const int i = i0 + t;
+        const bool live = i < npix;
+        const int p = live ? (y_min + i / size) * W + x_min + i % size : 0;
+        const bool hit = live && box[p] != 0;
+        const unsigned long long ballot = __ballot(hit);
+        __syncthreads();                               // red: the previous chunk's reads are done
+        if ((t & (kWave - 1)) == 0) red[t / kWave] = __popcll(ballot);
+        __syncthreads();
+        int wave_off = 0, chunk = 0;
+#pragma unroll
+        for (int w = 0; w < kBatchWaves; w++) {
+            if (w < t / kWave) wave_off += red[w];
+            chunk += red[w];
+        }
+        const int row = base + wave_off + lane_prefix(ballot);
+        base += chunk;
+        if (!live) continue;
+        const int64_t pix = (int64_t)patch * npix + i;
+        float rgb[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {                  // train.py:296-297, :398 in float64, one rounding per operator
+            const double a = __ddiv_rn((double)alpha[(size_t)p * 3 + c], 255.0);
+            const double fg = __dmul_rn(a, (double)image[(size_t)p * 3 + c]);
+            const double bk = __dmul_rn(__dsub_rn(1.0, a), bg[c]);
+            rgb[c] = (float)__ddiv_rn(__dadd_rn(fg, bk), 255.0);
+            out.target_patches[pix * 3 + c] = rgb[c];
+        }
+        out.patch_masks[pix] = hit ? 1 : 0;
+        out.row_of_pix[pix] = hit ? row : -1;
+        if (hit) {
+            const float *r8 = rays8 + (size_t)p * 8;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                out.rays[(int64_t)row * 3 + c] = r8[c];
+                out.rays[(rmax + row) * 3 + c] = r8[3 + c];
+                out.target_rgbs[(int64_t)row * 3 + c] = rgb[c];
+            }
+            out.near[row] = r8[6];
+            out.far[row] = r8[7];
+            out.pix_of_row[row] = (int32_t)pix;
+        }
+    }
+    if (patch == n_patches - 1 && t == 0) {
+        out.patch_div_indices[n_patches] = base;
+        out.n_rows[0] = base;
+    }
+}
+
+}  // namespace occ
+
+OCC_API int32_t occnerf_patch_batch_max_patches(void) { return occ::kMaxPatches; }
+
+OCC_API int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
+                                int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u,
+                                double subject_ratio, const float *h_bgcolor, int32_t *row_counts, float *rays, float *near,
+                                float *far, float *target_rgbs, float *target_patches, uint8_t *patch_masks,
+                                int32_t *patch_div_indices, int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix,
+                                int32_t *n_rows, void *stream) {
+    using namespace occ;
+    OCC_REQUIRE(image && alpha && rays8 && box_mask && h_u && h_bgcolor && row_counts && rays && near && far && target_rgbs &&
+                    target_patches && patch_masks && patch_div_indices && xy_min && pix_of_row && row_of_pix && n_rows,
+                "patch_batch: null argument");
+    OCC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < (1ll << 28), "patch_batch: bad image size %d x %d", H, W);
+    OCC_REQUIRE(n_patches >= 1 && n_patches <= kMaxPatches, "patch_batch: n_patches=%d outside [1, %d]", n_patches, kMaxPatches);
+    OCC_REQUIRE(size >= 1 && size <= H && size <= W, "patch_batch: patch size %d does not fit a %d x %d image", size, H, W);
+    PatchDraws draws;
+    for (int p = 0; p < n_patches; p++) {
+        draws.u[p][0] = h_u[p * 2];
+        draws.u[p][1] = h_u[p * 2 + 1];
+        OCC_REQUIRE(draws.u[p][0] >= 0.0 && draws.u[p][0] < 1.0 && draws.u[p][1] >= 0.0 && draws.u[p][1] < 1.0,
+                    "patch_batch: the uniforms of patch %d are not in [0, 1)", p);
+    }
+    for (int p = n_patches; p < kMaxPatches; p++) draws.u[p][0] = draws.u[p][1] = 0.0;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(batch_classify_kernel, dim3(H), dim3(kBatchThreads), 0, st, alpha, box_mask, H, W, row_counts);
+    hipLaunchKernelGGL(batch_pick_kernel, dim3(n_patches), dim3(kBatchThreads), 0, st, alpha, box_mask, H, W, size, draws,
+                       subject_ratio, (const int32_t *)row_counts, xy_min);
+    BatchOut out{rays, near, far, target_rgbs, target_patches, patch_masks, patch_div_indices, pix_of_row, row_of_pix, n_rows};
+    hipLaunchKernelGGL(batch_gather_kernel, dim3(n_patches), dim3(kBatchThreads), 0, st, image, alpha, rays8, box_mask, W,
+                       n_patches, size, (double)h_bgcolor[0], (double)h_bgcolor[1], (double)h_bgcolor[2],
+                       (const int32_t *)xy_min, out);
+    return check_launch("patch_batch");
+}

@@ -268,6 +268,22 @@ class PatchImages:
         self.pix_of_row = torch.from_numpy(pix.astype(np.int32)).to(device)
         self.row_of_pix = torch.from_numpy(inv).to(device)
 
+    @classmethod
+    def from_device_maps(cls, pix_of_row, row_of_pix, n_patches, size):
+        """The two maps as the device batch builder wrote them (ops.patch_batch: int32, pix_of_row[R] cut to the batch's row
+        count, row_of_pix[P * size^2]); nothing is copied or checked on the host."""
+        n = int(n_patches) * int(size) ** 2
+        for name, t in (('pix_of_row', pix_of_row), ('row_of_pix', row_of_pix)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 1 and t.is_contiguous()):
+                raise RuntimeError(f'PatchImages.from_device_maps: {name} must be a contiguous 1-D int32 device tensor')
+        if row_of_pix.shape[0] != n or pix_of_row.shape[0] > n:
+            raise RuntimeError(f'PatchImages.from_device_maps: {row_of_pix.shape[0]} pixels / {pix_of_row.shape[0]} rows do not '
+                               f'fit {n_patches} patches of {size} x {size}')
+        self = cls.__new__(cls)
+        self.n_patches, self.size = int(n_patches), int(size)
+        self.pix_of_row, self.row_of_pix = pix_of_row, row_of_pix
+        return self
+
     def assemble(self, rgb, bgcolor01):
         """img[P, size, size, 3] (the reference's _unpack_imgs layout): each row's rgb at its pixel, bgcolor01 elsewhere."""
         if rgb.dim() != 2 or rgb.shape != (self.pix_of_row.shape[0], 3):
@@ -282,6 +298,19 @@ def patch_image_loss(rgb, target, patches, bgcolor01, lossweights, lpips):
     with LPIPS's forward (the HIP module here; the tests pass a torch restatement)."""
     img = patches.assemble(rgb, bgcolor01)
     tgt = patches.assemble(target, bgcolor01)
+    loss = lossweights.get('mse', 0.0) * torch.mean((img - tgt) ** 2)
+    if lossweights.get('lpips', 0.0):
+        val = lpips(scale_for_lpips(img.permute(0, 3, 1, 2)), scale_for_lpips(tgt.permute(0, 3, 1, 2)))
+        loss = loss + lossweights['lpips'] * torch.mean(val)
+    return loss
+
+
+def patch_target_loss(rgb, target_patches, patches, bgcolor01, lossweights, lpips):
+    """patch_image_loss against target IMAGES, the reference trainer's own form (trainer.py:135-146 get_loss): the prediction
+    is assembled into the patch images (_unpack_imgs, :31-41), the target is the dataset's `target_patches` [P,S,S,3] itself
+    -- every pixel of the patch, also those without a ray, where the prediction holds bgcolor01."""
+    img = patches.assemble(rgb, bgcolor01)
+    tgt = target_patches.float()
     loss = lossweights.get('mse', 0.0) * torch.mean((img - tgt) ** 2)
     if lossweights.get('lpips', 0.0):
         val = lpips(scale_for_lpips(img.permute(0, 3, 1, 2)), scale_for_lpips(tgt.permute(0, 3, 1, 2)))

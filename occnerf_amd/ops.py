@@ -182,8 +182,9 @@ def _host_f64(vals, n):
     return a, a.ctypes.data_as(C.c_void_p)
 
 
-def gen_rays(K, E, H, W, bbox_min, bbox_max, device):
-    """All H*W pixel rays of a camera on the device -> rays8[H*W,8] (o, d, near, far), mask[H*W] uint8."""
+def gen_rays(K, E, H, W, bbox_min, bbox_max, device, out=None):
+    """All H*W pixel rays of a camera on the device -> rays8[H*W,8] (o, d, near, far), mask[H*W] uint8.
+    out=(rays8, mask): write into these buffers instead of new ones (the patch batch loader's resident pair)."""
     dev = torch.device(device)
     if dev.type != 'cuda':
         raise RuntimeError(f'gen_rays: needs a GPU device, got {dev}')
@@ -194,9 +195,15 @@ def gen_rays(K, E, H, W, bbox_min, bbox_max, device):
     t0, pt = _host_f64(E[:3, 3], 3)
     l0, pl = _host_f64(bbox_min, 3)
     h0, ph = _host_f64(bbox_max, 3)
-    rays8 = torch.empty(H * W, 8, device=dev, dtype=torch.float32)
-    mask = torch.empty(H * W, device=dev, dtype=torch.uint8)
-    with _guard_dev(dev):
+    if out is None:
+        rays8 = torch.empty(H * W, 8, device=dev, dtype=torch.float32)
+        mask = torch.empty(H * W, device=dev, dtype=torch.uint8)
+    else:
+        rays8, mask = out
+        _chk(rays8, torch.float32, 'rays8'), _chk(mask, torch.uint8, 'mask')
+        if rays8.numel() != H * W * 8 or mask.numel() != H * W or rays8.device != mask.device:
+            raise RuntimeError(f'gen_rays: out must be rays8[{H * W},8] and mask[{H * W}] on one device')
+    with _guard_dev(rays8.device):
         rc = _lib.lib().occnerf_gen_rays(pk, pr, pt, f32, int(H), int(W), pl, ph, rays8.data_ptr(),
                                          mask.data_ptr(), _stream(rays8))
     _lib.check(rc, 'gen_rays')
@@ -974,3 +981,62 @@ def patch_assemble_backward(d_img, pix_of_row):
                                                         _stream(d_img))
     _lib.check(rc, 'patch_assemble_backward')
     return d_rgb
+
+
+# ------------------------------------------------------------------ the training batch of a prepared dataset frame
+PATCH_BATCH_KEYS = ('rays', 'near', 'far', 'target_rgbs', 'target_patches', 'patch_masks', 'patch_div_indices', 'xy_min',
+                    'pix_of_row', 'row_of_pix', 'n_rows')
+
+
+def alloc_patch_batch(n_patches, size, H, device):
+    """The buffers occnerf_patch_batch fills, sized for R = n_patches * size^2 rows, plus its row-count scratch."""
+    N, S = int(n_patches), int(size)
+    rmax = N * S * S
+    f32 = dict(device=device, dtype=torch.float32)
+    i32 = dict(device=device, dtype=torch.int32)
+    return {'rays': torch.zeros(2, rmax, 3, **f32), 'near': torch.zeros(rmax, 1, **f32), 'far': torch.zeros(rmax, 1, **f32),
+            'target_rgbs': torch.zeros(rmax, 3, **f32), 'target_patches': torch.zeros(N, S, S, 3, **f32),
+            'patch_masks': torch.zeros(N, S, S, device=device, dtype=torch.bool),
+            'patch_div_indices': torch.zeros(N + 1, **i32), 'xy_min': torch.zeros(N, 2, **i32),
+            'pix_of_row': torch.zeros(rmax, **i32), 'row_of_pix': torch.zeros(rmax, **i32), 'n_rows': torch.zeros(1, **i32),
+            'row_counts': torch.zeros(2 * int(H), **i32)}
+
+
+def patch_batch(image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio, bgcolor, out=None):
+    """The patch batch of one frame (include/occnerf_hip.h occnerf_patch_batch): image / alpha [H,W,3] uint8 on the device,
+    rays8 / box_mask from gen_rays, u[n_patches,2] host uniforms in [0, 1), bgcolor[3] in 0..255 on the host.  -> the dict of
+    alloc_patch_batch (filled in place when passed as `out`); the row count stays on the device in 'n_rows'."""
+    H, W = int(image.shape[0]), int(image.shape[1])
+    N, S = int(n_patches), int(size)
+    if tuple(image.shape) != (H, W, 3) or tuple(alpha.shape) != (H, W, 3):
+        raise RuntimeError(f'patch_batch: image and alpha must both be [H,W,3], got {tuple(image.shape)}, {tuple(alpha.shape)}')
+    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
+        raise RuntimeError(f'patch_batch: rays8 / box_mask are not those of a {H} x {W} frame')
+    if out is None:
+        out = alloc_patch_batch(N, S, H, image.device)
+    if out['target_patches'].shape != (N, S, S, 3) or out['row_counts'].numel() < 2 * H:
+        raise RuntimeError('patch_batch: `out` was allocated for another patch count, patch size or image height')
+    u0 = np.ascontiguousarray(np.asarray(u, dtype=np.float64).reshape(-1))
+    if u0.size != 2 * N:
+        raise RuntimeError(f'patch_batch: u must be [{N},2], got {np.asarray(u).shape}')
+    bg, bgp = _host_f32(bgcolor, 3)
+    floats = ('rays', 'near', 'far', 'target_rgbs', 'target_patches')
+    ptr = {k: _chk(out[k], torch.bool if k == 'patch_masks' else torch.float32 if k in floats else torch.int32, k)
+           for k in PATCH_BATCH_KEYS + ('row_counts',)}
+    if any(out[k].device != image.device for k in ptr):
+        raise RuntimeError('patch_batch: `out` is on another device than the frame')
+    rmax = N * S * S
+    want = {'rays': 6 * rmax, 'near': rmax, 'far': rmax, 'target_rgbs': 3 * rmax, 'target_patches': 3 * rmax,
+            'patch_masks': rmax, 'patch_div_indices': N + 1, 'xy_min': 2 * N, 'pix_of_row': rmax, 'row_of_pix': rmax, 'n_rows': 1}
+    for k, n in want.items():
+        if out[k].numel() != n:
+            raise RuntimeError(f'patch_batch: out[{k!r}] holds {out[k].numel()} elements, the batch needs {n}')
+    with _guard(image):
+        rc = _lib.lib().occnerf_patch_batch(
+            _chk(image, torch.uint8, 'image'), _chk(alpha, torch.uint8, 'alpha'), _chk(rays8, torch.float32, 'rays8'),
+            _chk(box_mask, torch.uint8, 'box_mask'), H, W, N, S, u0.ctypes.data_as(C.c_void_p), float(subject_ratio), bgp,
+            ptr['row_counts'], ptr['rays'], ptr['near'], ptr['far'], ptr['target_rgbs'], ptr['target_patches'],
+            ptr['patch_masks'], ptr['patch_div_indices'], ptr['xy_min'], ptr['pix_of_row'], ptr['row_of_pix'], ptr['n_rows'],
+            _stream(image))
+    _lib.check(rc, 'patch_batch')
+    return out

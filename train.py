@@ -16,7 +16,13 @@ mse * MSE + lpips * mean(LPIPS-VGG) on those images (inputs scaled to [-1, 1]) +
 e.g. `train.lossweights "{'lpips': 1.0, 'mse': 0.2, 'comp': 1.0}"`.  LPIPS runs on the HIP kernels of
 occnerf_amd/lpips.py; its weights come from train.lpips_model_path (the v0.1 vgg.pth lin layers) and
 train.lpips_vgg16_path (a torchvision VGG16 state_dict), each a seeded stand-in when unset.  Without
-`lpips` the step is the ray-wise MSE + comp one.  Checkpoints use the reference's layout
+`lpips` the step is the ray-wise MSE + comp one.
+
+With a prepared dataset configured (`train.dataset_path DIR`, or the reference's `train.dataset zju_<subject>_train` /
+`monocular_train`; occnerf_amd/dataset.py) the batches come from the device-side patch batch loader instead: the teacher is
+not built, the target is the dataset's blended image, and the image terms are the reference trainer's own
+(trainer.py:135-146: the prediction assembled into patch images against `target_patches`); without `lpips` the loss is the
+ray-wise MSE against `target_rgbs` + comp.  Checkpoints use the reference's layout
 ({'iter','network','optimizer'} -> experiments/.../latest.tar, trainer.py:398-406)."""
 import os
 import time
@@ -57,10 +63,69 @@ def patch_rays(frame, rng, n_patches=6, size=32):
     return patch_ray_selection(frame, rng, n_patches, size)
 
 
+def dataset_step_loss(net, batch, it, tc, lpips=None):
+    """Forward + loss of one step on a loader batch (occnerf_amd/dataset.py): trainer.py:135-146 with `lpips` in the loss
+    weights, the ray-wise MSE against `target_rgbs` without; + comp."""
+    from occnerf_amd.dataset import NETWORK_KEYS
+    weights = tc['lossweights']
+    out = net(**{k: batch[k] for k in NETWORK_KEYS}, iter_val=it)
+    if 'lpips' in weights:
+        from occnerf_amd.lpips import PatchImages, patch_target_loss
+        n_patches, size = batch['patch_masks'].shape[0], batch['patch_masks'].shape[1]
+        patches = PatchImages.from_device_maps(batch['pix_of_row'], batch['row_of_pix'], n_patches, size)
+        loss = patch_target_loss(out['rgb'], batch['target_patches'], patches, batch['bgcolor'] / 255., weights, lpips)
+    else:
+        loss = weights['mse'] * torch.mean((out['rgb'].float() - batch['target_rgbs']) ** 2)
+    return loss + weights.get('comp', 1.0) * out['comp_loss'].float().mean()
+
+
+def train_on_dataset(tc, dev, dataset_path):
+    """The optimisation loop on a prepared dataset: batches from create_dataloader('train'), built on the device one step
+    ahead; no teacher network exists in this mode."""
+    from core.data import create_dataloader
+    loader = create_dataloader('train')
+    ds = loader.dataset
+    print(f'dataset: {dataset_path}: {len(ds)} frames of {ds.width} x {ds.height}, {len(ds.epoch_frames)} per epoch; '
+          'targets are the dataset images (no teacher network)')
+    net = create_network()
+    net.generate_neural_points(ds.avg_betas)
+    net.load_state_dict(make_state_dict(net.point_base.detach().numpy(), float(net.bound), seed=0), strict=True)
+    net = net.to(dev).train()
+    opt = make_optimizer(net, tc)
+    cfg.perturb = 1.0
+    os.makedirs(cfg.logdir, exist_ok=True)
+    lpips = None
+    if 'lpips' in tc['lossweights']:
+        from occnerf_amd.lpips import make_training_lpips
+        lpips, what = make_training_lpips(tc['lpips_model_path'], tc['lpips_vgg16_path'], dev)
+        print(what)
+    t0 = time.time()
+    for it in range(1, int(tc['maxiter']) + 1):
+        batch = next(loader)
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast('cuda', dtype=torch.bfloat16, enabled=bool(tc['bf16'])):
+            loss = dataset_step_loss(net, batch, it, tc, lpips)
+        loss.backward()
+        opt.step(max_grad_norm=1.0)                                     # trainer.py:248-249
+        decay = 0.1 ** (it / (tc['lrate_decay'] * 1000))                # exp_decay.py:7-19
+        for grp in opt.param_groups:
+            grp['lr'] = grp['base_lr'] * decay
+        if it % int(tc['log_interval']) == 0 or it == 1:
+            print(f"iter {it:5d}  loss {float(loss):.6f}  rays {batch['n_rows']}  frame {batch['frame_name']}  "
+                  f'{time.time() - t0:.1f} s')
+    torch.save({'iter': it, 'network': net.state_dict(), 'optimizer': opt.state_dict()},
+               os.path.join(cfg.logdir, 'latest.tar'))
+    print('saved', os.path.join(cfg.logdir, 'latest.tar'))
+
+
 def main():
     tc = dict(TRAIN_DEFAULTS)
     tc.update({k: v for k, v in dict(cfg.get('train', {})).items() if k in TRAIN_DEFAULTS})
     dev = torch.device('cuda:0')
+    from occnerf_amd.dataset import resolve_dataset_path
+    dataset_path = resolve_dataset_path(cfg, 'train')
+    if dataset_path is not None:
+        return train_on_dataset(tc, dev, dataset_path)
     net = create_network()
     net.generate_neural_points(np.zeros(10, 'float32'))
     net.load_state_dict(make_state_dict(net.point_base.detach().numpy(), float(net.bound), seed=0), strict=True)
