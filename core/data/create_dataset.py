@@ -12,7 +12,9 @@ and the SMPL model are not redistributable, tools/make_synthetic_dataset.py writ
     create_dataset.py:31).  Its batches are built on the GPU, so next() needs one;
   * 'movement' / 'progress': whole-frame dicts (`ray_shoot_mode 'image'`) with `target_rgbs` and `ray_alpha`, under the
     skip / maxframes rules of create_dataset.py:32-42 (progress: every (total // 16)-th frame, 16 of them; under evaluate
-    the first 300; movement under evaluate switches the occlusion band off);
+    the first 300; movement under evaluate switches the occlusion band off).  The loader is occnerf_amd.dataset.WholeFrames:
+    iterating it gives the host dicts (numpy); sequence.frames_to_device -- run.py, eval.py -- asks it for `device_frames`
+    instead, which builds each frame on the GPU (csrc/frame.hip) one frame ahead of the render;
   * the cameras derived from a dataset frame (freeview, tpose, allview, backview) are not built."""
 import os
 

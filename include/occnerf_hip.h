@@ -676,6 +676,27 @@ int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, const float 
                         float *target_patches, uint8_t *patch_masks, int32_t *patch_div_indices, int32_t *xy_min,
                         int32_t *pix_of_row, int32_t *row_of_pix, int32_t *n_rows, void *stream);
 
+/* A whole frame of a prepared dataset, built on the device: the reference's `ray_shoot_mode 'image'` dict
+ * (core/data/occnerf/train.py:353-537 without the patch keys) and the per-pixel maps of eval.py:140-196.
+ * Inputs as for occnerf_patch_batch: image[H,W,3], alpha[H,W,3] uint8 (resident, the occlusion band already applied),
+ * rays8[H*W,8] and box_mask[H*W] as occnerf_gen_rays wrote them; HOST h_bgcolor[3] in 0..255.  H * W < 2^28.
+ * occnerf_whole_frame_count: row_start[H+1] int32 = the number of box pixels in the image rows above each row, row_start[H] = R
+ *   (one workgroup per row counts, one workgroup scans the rows in place).  The caller reads R from the device: it sets the
+ *   output shapes.
+ * occnerf_whole_frame_gather, with that row_start and R: the R rays in row-major pixel order (np.nonzero(ray_mask)'s) --
+ *   ray_index[R] int64 (flat pixel index, ascending), rays[2,R,3], near[R], far[R] (copies of rays8), target_rgbs[R,3] (the
+ *   float64 blend of occnerf_patch_batch, one rounding per operator, -> float32), ray_alpha[R,3] fp64 = m / 255. -- and, for
+ *   EVERY pixel, truth_u8[H,W,3] = uint8(255.f * clip(c, 0, 1)) with c the blended target inside the box and
+ *   float32(bgcolor / 255) outside (run.py:46-63 unpack_to_image's truth image), gt_vis[H,W] = float32(m0 / 255.) inside the
+ *   box and 0 outside, gt_alpha[H,W] = float32(m0 / 255.), m0 the mask's channel 0.  The body map of the metrics is box_mask.
+ *   R = 0 is legal (the ray outputs may then be NULL; the maps are all background).  A row past R is never written.
+ * No atomics, no host wait; bit-identical to numpy on the host (PreparedDataset.whole_frame, image.unpack_to_image). */
+int occnerf_whole_frame_count(const uint8_t *box_mask, int32_t H, int32_t W, int32_t *row_start, void *stream);
+int occnerf_whole_frame_gather(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
+                               int32_t H, int32_t W, const float *h_bgcolor, const int32_t *row_start, int32_t R,
+                               int64_t *ray_index, float *rays, float *near, float *far, float *target_rgbs,
+                               double *ray_alpha, uint8_t *truth_u8, float *gt_vis, float *gt_alpha, void *stream);
+
 /* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
  * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
  * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance

@@ -115,6 +115,7 @@ _DEFAULTS = {
     'train_fused_trunks': True,      # bf16 training step: the trunks' forward as one kernel (csrc/trunks.hip); False: ten layer passes
     'skip_empty_samples': True,      # drop samples whose motion-weight sum is exactly 0 (identical pixels)
     'device_rays': True,             # run.py: generate the frame's ray batch on the GPU (occnerf_amd/rays.py)
+    'device_frames': True,           # movement / progress / eval.py on a prepared dataset: build each frame on the GPU (csrc/frame.hip)
     'ray_patch_order': True,         # render rays in Morton-ordered pixel patches (any order is exact)
     'knn_culling': True,             # cluster-culled exact kNN (False: brute force)
     'knn_center_cache': True,        # kNN queries within a proven radius of the frame's collapse point take its cached lists (same bits)

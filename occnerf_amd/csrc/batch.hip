@@ -15,56 +15,15 @@
 //
 // The blend is the reference's float64 expression, one rounding per operator (the tree is built with -ffp-contract=off):
 //   ((m / 255.) * image + (1.0 - m / 255.) * bgcolor) / 255.  -> float32.
-#include "common.h"
+#include "batch_common.h"
 
 namespace occ {
 
-constexpr int kBatchThreads = 256;
-constexpr int kBatchWaves = kBatchThreads / kWave;
 constexpr int kMaxPatches = 64;
 
 struct PatchDraws {
     double u[kMaxPatches][2];
 };
-
-__device__ __forceinline__ int lane_prefix(unsigned long long ballot) {      // set bits of the lanes below this one
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// Sum over the workgroup of a per-thread flag count; every thread gets the total.  `red` holds kBatchWaves ints.
-__device__ __forceinline__ int block_sum(int v, int *red) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();                                   // red may still be read from the previous use
-    if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = v;
-    __syncthreads();
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < kBatchWaves; w++) s += red[w];
-    return s;
-}
-
-// Exclusive prefix of `v` in thread order and the workgroup total.
-__device__ __forceinline__ int block_excl_scan(int v, int *red, int &total) {
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    __syncthreads();
-    if (lane == kWave - 1) red[wave] = inc;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kBatchWaves; w++) {
-        if (w < wave) before += red[w];
-        all += red[w];
-    }
-    total = all;
-    return before + inc - v;
-}
 
 // class 0: subject, class 1: box and not subject
 __device__ __forceinline__ bool in_class(const uint8_t *__restrict__ alpha, const uint8_t *__restrict__ box, int p, int cls) {
@@ -198,27 +157,15 @@ __global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8
         const bool live = i < npix;
         const int p = live ? (y_min + i / size) * W + x_min + i % size : 0;
         const bool hit = live && box[p] != 0;
-        const unsigned long long ballot = __ballot(hit);
-        __syncthreads();                               // red: the previous chunk's reads are done
-        if ((t & (kWave - 1)) == 0) red[t / kWave] = __popcll(ballot);
-        __syncthreads();
-        int wave_off = 0, chunk = 0;
-#pragma unroll
-        for (int w = 0; w < kBatchWaves; w++) {
-            if (w < t / kWave) wave_off += red[w];
-            chunk += red[w];
-        }
-        const int row = base + wave_off + lane_prefix(ballot);
+        int chunk;
+        const int row = base + chunk_rank(hit, red, chunk);
         base += chunk;
         if (!live) continue;
         const int64_t pix = (int64_t)patch * npix + i;
         float rgb[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {                  // train.py:296-297, :398 in float64, one rounding per operator
-            const double a = __ddiv_rn((double)alpha[(size_t)p * 3 + c], 255.0);
-            const double fg = __dmul_rn(a, (double)image[(size_t)p * 3 + c]);
-            const double bk = __dmul_rn(__dsub_rn(1.0, a), bg[c]);
-            rgb[c] = (float)__ddiv_rn(__dadd_rn(fg, bk), 255.0);
+            rgb[c] = blend_target(alpha[(size_t)p * 3 + c], image[(size_t)p * 3 + c], bg[c]);
             out.target_patches[pix * 3 + c] = rgb[c];
         }
         out.patch_masks[pix] = hit ? 1 : 0;

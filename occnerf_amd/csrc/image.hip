@@ -6,18 +6,13 @@
 // One thread per pixel.  The rays of a frame are the pixels of ray_mask in ascending order, so a pixel finds its ray
 // (or learns that it has none) by a binary search in ray_index[R] -- 18 L2-resident probes at 512 x 512; no
 // pixel -> ray map has to be built or kept per camera.  Bound: HBM streaming, 16 B per ray in, 3 (+3) B per pixel out.
-#include "common.h"
+#include "batch_common.h"
 
 namespace occ {
 
 struct ImageParams {
     float bg[3];       // cfg.bgcolor / 255 as float32 (np.full(..., dtype='float32'))
 };
-
-__device__ __forceinline__ uint8_t to_8b(float x) {
-    x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);          // np.clip (NaN propagates in numpy; not produced by the renderer)
-    return (uint8_t)__fmul_rn(255.0f, x);
-}
 
 __global__ __launch_bounds__(256) void assemble_image_kernel(const float *__restrict__ rgb, const float *__restrict__ alpha,
                                                              const int64_t *__restrict__ ray_index, int64_t R, int64_t n_pixels,

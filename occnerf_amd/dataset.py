@@ -167,14 +167,27 @@ class PreparedDataset:
         self.dataset = self                          # run.py reads loader.dataset.avg_betas
         self._dev = None
         if self.device is not None:
-            dev = self.device
-            self._dev = {
-                'image': [torch.from_numpy(a).to(dev) for a in self.images],
-                'alpha': [torch.from_numpy(a).to(dev) for a in self.alphas],
-                'frame': [{k: torch.from_numpy(np.ascontiguousarray(f[k])).to(dev) for k in ('dst_Rs', 'dst_Ts', 'dst_posevec')}
-                          for f in self.frames],
-                'cnl_gtfms': torch.from_numpy(self.cnl_gtfms).to(dev),
-                'motion_weights_priors': torch.from_numpy(self.motion_weights_priors).to(dev)}
+            self.to_device(self.device)
+
+    def to_device(self, device):
+        """Upload the images, the masks (uint8 [H,W,3] each) and the per-frame constants; a second call for the same device
+        is free.  -> self."""
+        dev = torch.device(device)
+        if dev.type != 'cuda':
+            raise RuntimeError(f'PreparedDataset.to_device: {dev} is not a GPU; the host arrays are self.images / self.alphas')
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        if self._dev is not None and self.device == dev:
+            return self
+        self.device = dev
+        self._dev = {
+            'image': [torch.from_numpy(a).to(dev) for a in self.images],
+            'alpha': [torch.from_numpy(a).to(dev) for a in self.alphas],
+            'frame': [{k: torch.from_numpy(np.ascontiguousarray(f[k])).to(dev) for k in ('dst_Rs', 'dst_Ts', 'dst_posevec')}
+                      for f in self.frames],
+            'cnl_gtfms': torch.from_numpy(self.cnl_gtfms).to(dev),
+            'motion_weights_priors': torch.from_numpy(self.motion_weights_priors).to(dev)}
+        return self
 
     @staticmethod
     def skeleton_to_bbox(skeleton, bbox_offset):
@@ -245,6 +258,70 @@ class WholeFrames:
             for k, v in self.dataset.whole_frame(i, self.bgcolor).items():
                 batch[k] = [v] if isinstance(v, str) else v if np.isscalar(v) else torch.as_tensor(np.asarray(v))[None]
             yield batch
+
+    def device_frames(self, device, prefetch=True, data_type=None):
+        """The same frames built on the device (csrc/frame.hip through ops.whole_frame), as the
+        (data, key, meta) triples sequence.frames_to_device yields: `data` holds what Network.forward takes plus
+        `target_rgbs` and `ray_alpha`, as device tensors (the float[3] constants on the host); `meta` holds idx, ray_index,
+        width, height, frame_name, target_rgbs, ray_alpha and the maps truth_u8 / gt_vis / gt_alpha / body the metrics take.
+        Images, masks and per-frame constants are uploaded on first use.
+
+        prefetch=True: the rays, the box test and the row scan of frame t+1 run on a side stream, into the other of two
+        buffer sets, while the consumer renders frame t; its ray count is copied to pinned memory behind an event.  The
+        consumer waits on that event only, makes its stream wait for it and enqueues the gather there: the render stream is
+        never synchronised.  prefetch=False enqueues everything on the current stream and reads the count with one blocking
+        copy.  Both give identical tensors.  data_type 'movement' names the camera for the renderer's ray order, as
+        frames_to_device does.  A frame without a ray raises ValueError."""
+        from . import ops
+        ds = self.dataset.to_device(device)
+        dev, H, W, n = ds.device, ds.height, ds.width, len(ds)
+        bg = np.array(self.bgcolor, dtype='float32')
+        sets = [{'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
+                 'box': torch.empty(H * W, device=dev, dtype=torch.uint8),
+                 'row_start': torch.empty(H + 1, device=dev, dtype=torch.int32),
+                 'host': torch.empty(1, dtype=torch.int32).pin_memory(),
+                 'event': torch.cuda.Event()} for _ in range(2 if prefetch else 1)]
+        side = torch.cuda.Stream(device=dev) if prefetch else None
+
+        def enqueue(i):
+            """gen_rays, the count and the copy of R to pinned memory for frame i, on the current stream."""
+            bufs, f = sets[i % len(sets)], ds.frames[i]
+            ops.gen_rays(f['K'], f['E'], H, W, f['dst_bbox_min'], f['dst_bbox_max'], dev, out=(bufs['rays8'], bufs['box']))
+            ops.whole_frame_count(bufs['box'], H, W, bufs['row_start'])
+            bufs['host'].copy_(bufs['row_start'][H:], non_blocking=True)
+            bufs['event'].record()
+            return bufs
+
+        def start(i):
+            if side is None:
+                return enqueue(i)
+            # the buffer set was last read by the gather of frame i - 2, on the consumer's stream
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                return enqueue(i)
+
+        pending = start(0) if n else None
+        for i in range(n):
+            bufs = pending
+            bufs['event'].synchronize()
+            torch.cuda.current_stream(dev).wait_event(bufs['event'])
+            R = int(bufs['host'][0])
+            name = ds.frames[i]['frame_name']
+            if R == 0:
+                raise ValueError(f'frame {name}: no ray of its camera hits the box around the body (the box misses the '
+                                 f'{W} x {H} image); nothing to render')
+            out = ops.whole_frame(ds._dev['image'][i], ds._dev['alpha'][i], bufs['rays8'], bufs['box'], bg,
+                                  row_start=bufs['row_start'], R=R)
+            body = bufs['box'].view(H, W).clone()              # the buffer set is rewritten two frames on
+            pending = start(i + 1) if i + 1 < n else None
+            data = {'rays': out['rays'], 'near': out['near'], 'far': out['far'], 'bgcolor': torch.from_numpy(bg),
+                    'target_rgbs': out['target_rgbs'], 'ray_alpha': out['ray_alpha']}
+            data.update({k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v)
+                         for k, v in ds.device_constants(i).items()})
+            meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': name,
+                    'target_rgbs': out['target_rgbs'], 'ray_alpha': out['ray_alpha'], 'truth_u8': out['truth_u8'],
+                    'gt_vis': out['gt_vis'], 'gt_alpha': out['gt_alpha'], 'body': body}
+            yield data, ('movement', R) if data_type == 'movement' else None, meta
 
 
 class PatchBatchLoader:

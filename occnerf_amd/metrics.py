@@ -140,6 +140,30 @@ def frame_metrics(rgb, alpha, ray_index, target_rgb, width, height, *, ray_alpha
     return out
 
 
+def frame_metrics_from_maps(rgb, alpha, ray_index, maps, width, height, bgcolor=(1., 1., 1.), with_images=False,
+                            data_range=2.0):
+    """frame_metrics for a frame whose truth side is already on the device as per-pixel maps (a prepared dataset's
+    device_frames, csrc/frame.hip): maps['truth_u8'] uint8 [H,W,3], maps['body'] uint8 [H,W] (the box mask),
+    maps['gt_vis'] and maps['gt_alpha'] float32 [H,W].  Only the predicted image and the predicted alpha map are assembled
+    here.  The same seven numbers as frame_metrics(..., target_rgbs, ray_alpha=..., gt_alpha=...) on the host dict of the
+    frame, bit for bit: the kernel is handed the same bytes."""
+    from .image import assemble_uint8_device
+    shape = (int(height), int(width))
+    for k, dtype, tail in (('truth_u8', torch.uint8, (3,)), ('body', torch.uint8, ()), ('gt_vis', torch.float32, ()),
+                           ('gt_alpha', torch.float32, ())):
+        if k not in maps or tuple(maps[k].shape) != shape + tail or maps[k].dtype != dtype:
+            raise ValueError(f'frame_metrics_from_maps: maps[{k!r}] must be {dtype} {list(shape + tail)}')
+    rgb_img, alpha_img = assemble_uint8_device(width, height, ray_index, bgcolor, rgb, alpha, want_alpha=with_images)
+    alpha_map = pixel_map(ray_index, alpha.reshape(-1), height, width, torch.float32)
+    record, _ = _frame_metrics_raw(rgb_img, maps['truth_u8'], alpha_map, maps['body'], maps['gt_vis'], maps['gt_alpha'],
+                                   data_range)
+    vals = record[0, :len(KEYS)].cpu().numpy()
+    out = {k: float(v) for k, v in zip(KEYS, vals)}
+    if with_images:
+        return out, {'rgb': rgb_img, 'truth': maps['truth_u8'], 'alpha': alpha_img}
+    return out
+
+
 def batch_metrics(pred, truth, alpha=None, body=None, gt_vis=None, gt_alpha=None, data_range=2.0, want_map=False):
     """N same-size frames in one launch pair: pred, truth uint8 [N,H,W,3]; the maps [N,H,W] as occnerf_frame_metrics takes
     them (include/occnerf_hip.h).  -> (record float64 [N, 14] on the GPU: KEYS, then n_vis, n_body, intersection, union

@@ -1040,3 +1040,88 @@ def patch_batch(image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio
             _stream(image))
     _lib.check(rc, 'patch_batch')
     return out
+
+
+# ------------------------------------------------------------------ a whole frame of a prepared dataset
+WHOLE_FRAME_KEYS = ('ray_index', 'rays', 'near', 'far', 'target_rgbs', 'ray_alpha', 'truth_u8', 'gt_vis', 'gt_alpha')
+
+
+def _whole_frame_shapes(H, W, R):
+    return {'ray_index': ((R,), torch.int64), 'rays': ((2, R, 3), torch.float32), 'near': ((R, 1), torch.float32),
+            'far': ((R, 1), torch.float32), 'target_rgbs': ((R, 3), torch.float32), 'ray_alpha': ((R, 3), torch.float64),
+            'truth_u8': ((H, W, 3), torch.uint8), 'gt_vis': ((H, W), torch.float32), 'gt_alpha': ((H, W), torch.float32)}
+
+
+def alloc_whole_frame(H, W, R, device):
+    """The buffers occnerf_whole_frame_gather fills for a frame of R rays."""
+    return {k: torch.empty(shape, device=device, dtype=dtype) for k, (shape, dtype) in _whole_frame_shapes(H, W, R).items()}
+
+
+def whole_frame_count(box_mask, H, W, row_start=None):
+    """row_start int32 [H+1] on the device: the box pixels above every image row, row_start[H] = the frame's ray count R
+    (include/occnerf_hip.h occnerf_whole_frame_count).  Nothing is read back here."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H * W >= 1 << 28:
+        raise RuntimeError(f'whole_frame: H*W = {H} * {W} must be in [1, 2^28)')
+    ptr = _chk(box_mask, torch.uint8, 'box_mask')
+    if box_mask.numel() != H * W:
+        raise RuntimeError(f'whole_frame: box_mask holds {box_mask.numel()} entries, a {H} x {W} frame has {H * W}')
+    if row_start is None:
+        row_start = torch.empty(H + 1, device=box_mask.device, dtype=torch.int32)
+    rs = _chk(row_start, torch.int32, 'row_start')
+    if row_start.numel() != H + 1 or row_start.device != box_mask.device:
+        raise RuntimeError(f'whole_frame: row_start must be int32 [{H + 1}] on the device of box_mask')
+    with _guard(box_mask):
+        rc = _lib.lib().occnerf_whole_frame_count(ptr, H, W, rs, _stream(box_mask))
+    _lib.check(rc, 'whole_frame_count')
+    return row_start
+
+
+def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, out=None):
+    """One frame of a prepared dataset as PreparedDataset.whole_frame() builds it on the host, plus the per-pixel maps of the
+    metrics (include/occnerf_hip.h occnerf_whole_frame_gather): image / alpha [H,W,3] uint8 on the device, rays8 / box_mask
+    from gen_rays, bgcolor[3] in 0..255 on the host.  -> dict of WHOLE_FRAME_KEYS.
+    row_start, R: the result of whole_frame_count and the host copy of row_start[H] (the loader reads it from pinned memory
+    behind an event); both None: counted here and read back with one blocking copy.  out: a dict of alloc_whole_frame(H, W, R)
+    to fill in place."""
+    if not torch.is_tensor(image) or not torch.is_tensor(alpha) or image.dim() != 3 or alpha.dim() != 3:
+        raise RuntimeError('whole_frame: image and alpha must be [H,W,3] tensors')
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if tuple(image.shape) != (H, W, 3) or tuple(alpha.shape) != (H, W, 3):
+        raise RuntimeError(f'whole_frame: image and alpha must both be [H,W,3], got {tuple(image.shape)}, {tuple(alpha.shape)}')
+    if H * W >= 1 << 28:
+        raise RuntimeError(f'whole_frame: H*W = {H} * {W} must be below 2^28')
+    pi, pa = _chk(image, torch.uint8, 'image'), _chk(alpha, torch.uint8, 'alpha')
+    pr, pb = _chk(rays8, torch.float32, 'rays8'), _chk(box_mask, torch.uint8, 'box_mask')
+    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
+        raise RuntimeError(f'whole_frame: rays8 / box_mask are not those of a {H} x {W} frame')
+    if any(t.device != image.device for t in (alpha, rays8, box_mask)):
+        raise RuntimeError('whole_frame: image, alpha, rays8 and box_mask must be on one device')
+    if (row_start is None) != (R is None):
+        raise RuntimeError('whole_frame: row_start and R come together (whole_frame_count and its row_start[H])')
+    if row_start is None:
+        row_start = whole_frame_count(box_mask, H, W)
+        R = int(row_start[H].item())
+    R = int(R)
+    ps = _chk(row_start, torch.int32, 'row_start')
+    if row_start.numel() != H + 1 or row_start.device != image.device:
+        raise RuntimeError(f'whole_frame: row_start must be int32 [{H + 1}] on the frame\'s device')
+    if R < 0 or R > H * W:
+        raise RuntimeError(f'whole_frame: R = {R} is outside [0, {H * W}]')
+    if out is None:
+        out = alloc_whole_frame(H, W, R, image.device)
+    ptr = {}
+    for k, (shape, dtype) in _whole_frame_shapes(H, W, R).items():
+        if k not in out or not torch.is_tensor(out[k]) or tuple(out[k].shape) != shape:
+            got = tuple(out[k].shape) if k in out and torch.is_tensor(out[k]) else None
+            raise RuntimeError(f'whole_frame: out[{k!r}] must be {shape} for R = {R}, got {got}')
+        ptr[k] = _chk(out[k], dtype, k)
+        if out[k].device != image.device:
+            raise RuntimeError('whole_frame: `out` is on another device than the frame')
+    bg, bgp = _host_f32(bgcolor, 3)
+    with _guard(image):
+        rc = _lib.lib().occnerf_whole_frame_gather(
+            pi, pa, pr, pb, H, W, bgp, ps, R, ptr['ray_index'], ptr['rays'], ptr['near'], ptr['far'], ptr['target_rgbs'],
+            ptr['ray_alpha'], ptr['truth_u8'], ptr['gt_vis'], ptr['gt_alpha'], _stream(image))
+    _lib.check(rc, 'whole_frame_gather')
+    return out

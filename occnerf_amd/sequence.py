@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .config import get_cfg
 from .rays import frame_rays
 
 EXCLUDE_KEYS_TO_GPU = ['frame_name', 'img_width', 'img_height', 'ray_mask',
@@ -64,7 +65,13 @@ class SyntheticFrames:
 
 def frames_to_device(loader, data_type, device='cuda'):
     """The loader's frames as (renderer inputs, camera key, bookkeeping): tensors on the device (asynchronously), the three
-    float[3] constants by value, the ray batch generated on the GPU when the loader hands over a camera instead of rays."""
+    float[3] constants by value, the ray batch generated on the GPU when the loader hands over a camera instead of rays.
+    A loader with `device_frames` (a prepared dataset's WholeFrames) builds its frames on the GPU instead (csrc/frame.hip)
+    unless `device_frames False` is configured or the device is the host; `meta` then also carries frame_name, target_rgbs,
+    ray_alpha and the per-pixel maps of the metrics."""
+    if hasattr(loader, 'device_frames') and torch.device(device).type == 'cuda' and get_cfg().get('device_frames', True):
+        yield from loader.device_frames(device, prefetch=True, data_type=data_type)
+        return
     for idx, batch in enumerate(loader):
         batch = {k: (v[0] if torch.is_tensor(v) or isinstance(v, list) else v) for k, v in batch.items()}
         data = {k: (v if k in HOST_KEYS else v.to(device, non_blocking=True)) for k, v in batch.items()

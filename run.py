@@ -21,6 +21,7 @@ cfg.bgcolor = [255., 255., 255.]
 
 from core.data import create_dataloader  # noqa: E402
 from core.nets import create_network  # noqa: E402
+from occnerf_amd.dataset import resolve_dataset_path  # noqa: E402
 from occnerf_amd.image import ImageWriter, assemble_uint8_device  # noqa: E402
 from occnerf_amd.parallel import ShardedRenderer  # noqa: E402
 from occnerf_amd.sequence import frames_to_device, render_sequence  # noqa: E402
@@ -169,16 +170,18 @@ def run_evaluate():
     """run.py:194-244: PSNR of the rendered rays against the frames' target colours over the `progress` frames (frames
     4 and 15 skipped, the network called with iter_val = 1 exactly as the reference does, run.py:224-230: pose refinement
     and the non-rigid condition are then below their kick-in iterations).  The targets are the teacher's render
-    (`_teacher`).  The paper's metrics -- PSNR and SSIM over the vis / body / full pixels and the silhouette IoU, the
-    reference's eval.py -- are computed by eval.py at the repository root."""
+    (`_teacher`) on the synthetic source and the frames' own `target_rgbs` (the photographs) on a prepared dataset.  The
+    paper's metrics -- PSNR and SSIM over the vis / body / full pixels and the silhouette IoU, the reference's eval.py --
+    are computed by eval.py at the repository root."""
     rank, world, model, loader, renderer, dev = _setup('progress', evaluate=True)
-    teach = _teacher(loader, dev)
+    on_dataset = resolve_dataset_path(cfg, 'progress') is not None
+    teach = None if on_dataset else _teacher(loader, dev)
     psnrs, skips = [], [4, 15]
     with torch.no_grad():
         for data, key, meta in frames_to_device(loader, 'progress', dev):
             if meta['idx'] in skips:
                 continue
-            target = teach.finish(teach.submit(data, iter_val=cfg.eval_iter))
+            target = {'rgb': data['target_rgbs']} if on_dataset else teach.finish(teach.submit(data, iter_val=cfg.eval_iter))
             out = renderer.finish(renderer.submit(data, iter_val=1))       # run.py:224 `batch['iter_val'] = torch.full((1,), 1)`
             if out is not None:
                 psnrs.append(PSNR(out['rgb'], target['rgb'], 1.))
