@@ -150,7 +150,7 @@ def canonical_mlp_torch(cm, xyz, knn_idxs, net, knn_base, point_sdf):
 def raw2outputs(raw, mask, z_vals, rays_d, bgcolor):
     """network.py:320-348."""
     dists = z_vals[..., 1:] - z_vals[..., :-1]
-    dists = torch.cat([dists, torch.full_like(dists[..., :1], 1e10)], dim=-1)
+    dists = torch.cat([dists, torch.full_like(z_vals[..., :1], 1e10)], dim=-1)      # (z_vals: a ray of one sample has no dists)
     dists = dists * torch.norm(rays_d[..., None, :], dim=-1)
     rgb = torch.sigmoid(raw[..., :3])
     alpha = (1.0 - torch.exp(-F.softplus(raw[..., 3]) * dists)) * mask[:, :, 0]
