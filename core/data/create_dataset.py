@@ -15,7 +15,9 @@ and the SMPL model are not redistributable, tools/make_synthetic_dataset.py writ
     the first 300; movement under evaluate switches the occlusion band off).  The loader is occnerf_amd.dataset.WholeFrames:
     iterating it gives the host dicts (numpy); sequence.frames_to_device -- run.py, eval.py -- asks it for `device_frames`
     instead, which builds each frame on the GPU (csrc/frame.hip) one frame ahead of the render;
-  * the cameras derived from a dataset frame (freeview, tpose, allview, backview) are not built."""
+  * 'freeview' / 'backview' / 'allview' / 'tpose': the cameras derived from a dataset frame (occnerf_amd.views.ViewFrames,
+    the reference's freeview.py / backview.py / allview.py / tpose.py).  Host dicts when iterated; `device_frames` builds
+    the rays on the GPU (csrc/view.hip).  backview reads the directory movement would; allview also needs all_cameras.pkl."""
 import os
 
 import torch
@@ -23,6 +25,7 @@ import torch
 from configs import cfg
 from occnerf_amd.dataset import PatchBatchLoader, PreparedDataset, WholeFrames, resolve_dataset_path
 from occnerf_amd.sequence import SyntheticFrames
+from occnerf_amd.views import KINDS as VIEW_KINDS, ViewFrames
 
 
 def _prepared(data_type, evaluate, path):
@@ -35,10 +38,11 @@ def _prepared(data_type, evaluate, path):
                                 sample_subject_ratio=float(cfg.patch.sample_subject_ratio), bgcolor=None,
                                 seed=int(dict(cfg.get('train', {})).get('seed', 0)),
                                 prefetch=bool(dict(cfg.get('train', {})).get('prefetch', True)))
+    if data_type in VIEW_KINDS:
+        return ViewFrames.from_cfg(cfg, path, data_type)
     if data_type not in ('movement', 'progress'):
-        raise NotImplementedError(f"type '{data_type}' on the prepared dataset '{path}': only train / movement / progress "
-                                  'read a dataset; the freeview / tpose / allview / backview cameras derived from a dataset '
-                                  'frame are not built')
+        raise NotImplementedError(f"type '{data_type}' on the prepared dataset '{path}': train, movement, progress, "
+                                  'freeview, backview, allview and tpose read a dataset')
     skip, maxframes = 1, -1
     if data_type == 'progress':
         total = len([f for f in os.listdir(os.path.join(path, 'images')) if f.endswith('.png')])
@@ -49,7 +53,8 @@ def _prepared(data_type, evaluate, path):
 
 
 def create_dataloader(data_type='train', evaluate=False, **_):
-    path = resolve_dataset_path(cfg, data_type)
+    # backview has no dataset node of its own in the reference's configs: it reads the directory movement would
+    path = resolve_dataset_path(cfg, 'movement' if data_type == 'backview' else data_type)
     if path is not None:
         return _prepared(data_type, evaluate, path)
     if cfg.get('dataset', 'synthetic') != 'synthetic' or \

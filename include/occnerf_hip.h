@@ -697,6 +697,15 @@ int occnerf_whole_frame_gather(const uint8_t *image, const uint8_t *alpha, const
                                int64_t *ray_index, float *rays, float *near, float *far, float *target_rgbs,
                                double *ray_alpha, uint8_t *truth_u8, float *gt_vis, float *gt_alpha, void *stream);
 
+/* The rays of a camera that has no photograph (freeview / backview / allview / tpose on a prepared dataset): the rays-only
+ * form of occnerf_whole_frame_gather.  rays8[H*W,8] and box_mask[H*W] as occnerf_gen_rays wrote them, row_start[H+1] and R
+ * from occnerf_whole_frame_count.  One workgroup per image row -> ray_index[R] int64 (flat pixel index, ascending),
+ * rays[2,R,3], near[R], far[R] (copies of rays8) in row-major pixel order, np.nonzero(ray_mask)'s.  No image is read and no
+ * per-pixel map is written.  R = 0 is legal (the outputs may then be NULL).  A row past R is never written.  H * W < 2^28.
+ * No atomics, no host wait. */
+int occnerf_view_frame_gather(const float *rays8, const uint8_t *box_mask, int32_t H, int32_t W, const int32_t *row_start,
+                              int32_t R, int64_t *ray_index, float *rays, float *near, float *far, void *stream);
+
 /* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
  * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
  * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance

@@ -86,7 +86,9 @@ _DEFAULTS = {
     'N_samples': 128, 'perturb': 1.0, 'netchunk_per_gpu': 300000, 'chunk': 32768, 'n_gpus': 1,
     'bgcolor': [0.0, 0.0, 0.0], 'resize_img_scale': 0.5, 'show_alpha': False, 'show_truth': False,
     'patch': {'sample_subject_ratio': 0.8, 'N_patches': 6, 'size': 32},
-    'freeview': {'frame_idx': 0}, 'tpose': {}, 'movement': {},
+    # freeview.src_type: the orbit of the derived cameras (occnerf_amd/views.py) when only train.dataset_path names the
+    # dataset: 'zju_mocap' (axis z, inverted angle) or 'wild' (axis y); zju_* / monocular_* dataset names decide it themselves
+    'freeview': {'frame_idx': 0, 'src_type': 'zju_mocap'}, 'tpose': {}, 'movement': {},
     # train.dataset_path: a prepared dataset directory (occnerf_amd/dataset.py) -- train.py then trains on it and `movement` /
     # `progress` read it; None: the synthetic subject.  train.images_prescaled: with resize_img_scale != 1, the PNGs are
     # already at the training size (only K is scaled; nothing is resized here)

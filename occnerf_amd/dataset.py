@@ -63,13 +63,33 @@ def occlusion_columns(occlusion, W):
     return slice(mid - width // 2, mid + width // 2).indices(W)[:2]
 
 
+def skeleton_to_bbox(skeleton, bbox_offset):
+    return {'min_xyz': np.min(skeleton, axis=0) - bbox_offset, 'max_xyz': np.max(skeleton, axis=0) + bbox_offset}
+
+
+def load_canonical(dataset_path, bbox_offset=0.3, volume_size=32):
+    """What canonical_joints.pkl alone determines (train.py:96-113, :503-535), as the attributes PreparedDataset carries:
+    canonical_joints, avg_betas, canonical_bbox, motion_weights_priors, cnl_gtfms and the three float32 box constants."""
+    with open(os.path.join(dataset_path, 'canonical_joints.pkl'), 'rb') as f:
+        cnl = pickle.load(f)
+    joints = cnl['joints'].astype('float32')
+    bbox = skeleton_to_bbox(joints, bbox_offset)
+    mn, mx = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
+    return {'canonical_joints': joints, 'avg_betas': cnl['avg_betas'].astype('float32'), 'canonical_bbox': bbox,
+            'motion_weights_priors': synth.approx_gaussian_bone_volumes(
+                joints, bbox['min_xyz'], bbox['max_xyz'], grid_size=int(volume_size)).astype('float32'),
+            'cnl_gtfms': synth.get_canonical_global_tfms(joints),
+            'cnl_bbox_min_xyz': mn, 'cnl_bbox_max_xyz': mx, 'cnl_bbox_scale_xyz': 2.0 / (mx - mn)}
+
+
 class PreparedDataset:
     """A prepared directory, opened once.
 
     The frame list is the sorted PNG names, then [::skip], then [:maxframes] (train.py:68-75).  Per frame, on the host:
     the joints box +- bbox_offset (:115-133), K with K[:2] *= resize_img_scale (:430), E through apply_global_tfm_to_camera,
     dst_Rs / dst_Ts / cnl_gtfms / dst_posevec = poses[3:] + 1e-2 (:503-535); per subject the canonical box, its scale and
-    motion_weights_priors.  Image and mask are uploaded as uint8 [H,W,3] each (6 bytes per pixel).
+    motion_weights_priors.  The raw `extrinsics` and the axis-angle `Rh_vec` are kept too (views.py derives cameras from
+    them).  Image and mask are uploaded as uint8 [H,W,3] each (6 bytes per pixel).
 
     The simulated occlusion (:286-287) zeroes the mask columns [mid - width//2, mid + width//2) of the frames whose POSITION
     in the frame list (not their frame number) is below occlusion.range when `occlude` is set; it is constant per frame, so
@@ -94,7 +114,7 @@ class PreparedDataset:
         if upsample_pc:
             raise NotImplementedError('upsample_pc: subdividing the SMPL mesh (train.py:384-385) needs trimesh and the SMPL '
                                       'faces; not built')
-        scale = float(resize_img_scale)
+        scale = self.resize_img_scale = float(resize_img_scale)
         if scale != 1.0 and not images_prescaled:
             raise NotImplementedError(
                 f'resize_img_scale={scale}: the reference resizes the blended image with cv2 (train.py:306-314), which is not '
@@ -105,16 +125,7 @@ class PreparedDataset:
             with open(os.path.join(dataset_path, name), 'rb') as f:
                 return pickle.load(f)
 
-        cnl = load('canonical_joints.pkl')
-        self.canonical_joints = cnl['joints'].astype('float32')
-        self.avg_betas = cnl['avg_betas'].astype('float32')
-        self.canonical_bbox = self.skeleton_to_bbox(self.canonical_joints, bbox_offset)
-        self.motion_weights_priors = synth.approx_gaussian_bone_volumes(
-            self.canonical_joints, self.canonical_bbox['min_xyz'], self.canonical_bbox['max_xyz'],
-            grid_size=int(volume_size)).astype('float32')
-        self.cnl_gtfms = synth.get_canonical_global_tfms(self.canonical_joints)
-        mn, mx = self.canonical_bbox['min_xyz'].astype('float32'), self.canonical_bbox['max_xyz'].astype('float32')
-        self.cnl_bbox_min_xyz, self.cnl_bbox_max_xyz, self.cnl_bbox_scale_xyz = mn, mx, 2.0 / (mx - mn)
+        self.__dict__.update(load_canonical(dataset_path, bbox_offset, volume_size))
         cameras, mesh_infos = load('cameras.pkl'), load('mesh_infos.pkl')
 
         names = sorted(os.path.splitext(f)[0] for f in os.listdir(os.path.join(dataset_path, 'images'))
@@ -158,7 +169,9 @@ class PreparedDataset:
                 'dst_bbox_min': bbox['min_xyz'], 'dst_bbox_max': bbox['max_xyz'], 'joints': joints, 'poses': poses,
                 'betas': info['betas'].astype('float32'), 'Rh': synth.rodrigues_exact(Rh).astype(np.float32), 'Th': Th,
                 'dst_Rs': dst_Rs, 'dst_Ts': dst_Ts, 'dst_posevec': poses[3:] + 1e-2,
-                'empty': int(alpha.astype(np.int64).sum()) < 255})
+                'empty': int(alpha.astype(np.int64).sum()) < 255,
+                # what the derived cameras of views.py start from: the camera as calibrated and the body's axis-angle Rh
+                'extrinsics': np.asarray(cameras[name]['extrinsics']), 'Rh_vec': Rh})
             self.images.append(np.ascontiguousarray(img))
             self.alphas.append(np.ascontiguousarray(alpha))
         self.epoch_frames = [i for i, f in enumerate(self.frames) if not f['empty']]
@@ -189,9 +202,7 @@ class PreparedDataset:
             'motion_weights_priors': torch.from_numpy(self.motion_weights_priors).to(dev)}
         return self
 
-    @staticmethod
-    def skeleton_to_bbox(skeleton, bbox_offset):
-        return {'min_xyz': np.min(skeleton, axis=0) - bbox_offset, 'max_xyz': np.max(skeleton, axis=0) + bbox_offset}
+    skeleton_to_bbox = staticmethod(skeleton_to_bbox)
 
     @classmethod
     def from_cfg(cls, cfg, dataset_path, device='cuda:0', skip=1, maxframes=-1):

@@ -1125,3 +1125,38 @@ def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, 
             ptr['ray_alpha'], ptr['truth_u8'], ptr['gt_vis'], ptr['gt_alpha'], _stream(image))
     _lib.check(rc, 'whole_frame_gather')
     return out
+
+
+# ------------------------------------------------------------------ the rays of a camera without a photograph
+def view_frame(rays8, box_mask, H, W, row_start=None, R=None):
+    """The rays of a novel view (include/occnerf_hip.h occnerf_view_frame_gather): rays8 / box_mask from gen_rays for an
+    H x W camera -> {'ray_index' int64 [R], 'rays' [2,R,3], 'near' [R,1], 'far' [R,1]}, the box hits in np.nonzero order.
+    No image is read and no per-pixel map written.  row_start, R: as for whole_frame (whole_frame_count's result and the host
+    copy of row_start[H]); both None: counted here and read back with one blocking copy."""
+    H, W = int(H), int(W)
+    if H <= 0 or W <= 0 or H * W >= 1 << 28:
+        raise RuntimeError(f'view_frame: H*W = {H} * {W} must be in [1, 2^28)')
+    pr, pb = _chk(rays8, torch.float32, 'rays8'), _chk(box_mask, torch.uint8, 'box_mask')
+    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
+        raise RuntimeError(f'view_frame: rays8 / box_mask are not those of a {H} x {W} frame')
+    if rays8.device != box_mask.device:
+        raise RuntimeError('view_frame: rays8 and box_mask must be on one device')
+    if (row_start is None) != (R is None):
+        raise RuntimeError('view_frame: row_start and R come together (whole_frame_count and its row_start[H])')
+    if row_start is None:
+        row_start = whole_frame_count(box_mask, H, W)
+        R = int(row_start[H].item())
+    R = int(R)
+    ps = _chk(row_start, torch.int32, 'row_start')
+    if row_start.numel() != H + 1 or row_start.device != rays8.device:
+        raise RuntimeError(f'view_frame: row_start must be int32 [{H + 1}] on the frame\'s device')
+    if R < 0 or R > H * W:
+        raise RuntimeError(f'view_frame: R = {R} is outside [0, {H * W}]')
+    dev = rays8.device
+    out = {'ray_index': torch.empty(R, device=dev, dtype=torch.int64), 'rays': torch.empty(2, R, 3, device=dev),
+           'near': torch.empty(R, 1, device=dev), 'far': torch.empty(R, 1, device=dev)}
+    with _guard(rays8):
+        rc = _lib.lib().occnerf_view_frame_gather(pr, pb, H, W, ps, R, out['ray_index'].data_ptr(), out['rays'].data_ptr(),
+                                                  out['near'].data_ptr(), out['far'].data_ptr(), _stream(rays8))
+    _lib.check(rc, 'view_frame_gather')
+    return out

@@ -14,7 +14,7 @@ from .config import get_cfg
 from .rays import frame_rays
 
 EXCLUDE_KEYS_TO_GPU = ['frame_name', 'img_width', 'img_height', 'ray_mask',
-                       'camera_K', 'camera_E', 'dst_bbox_min', 'dst_bbox_max']
+                       'camera_K', 'camera_E', 'dst_bbox_min', 'dst_bbox_max', 'truth_u8']
 HOST_KEYS = ('bgcolor', 'cnl_bbox_min_xyz', 'cnl_bbox_max_xyz', 'cnl_bbox_scale_xyz')   # float[3]: taken by value
 
 
@@ -68,7 +68,8 @@ def frames_to_device(loader, data_type, device='cuda'):
     float[3] constants by value, the ray batch generated on the GPU when the loader hands over a camera instead of rays.
     A loader with `device_frames` (a prepared dataset's WholeFrames) builds its frames on the GPU instead (csrc/frame.hip)
     unless `device_frames False` is configured or the device is the host; `meta` then also carries frame_name, target_rgbs,
-    ray_alpha and the per-pixel maps of the metrics."""
+    ray_alpha and the per-pixel maps of the metrics (WholeFrames), or frame_name and the photograph truth_u8 (views.py's
+    ViewFrames, which hands truth_u8 over on the host path too)."""
     if hasattr(loader, 'device_frames') and torch.device(device).type == 'cuda' and get_cfg().get('device_frames', True):
         yield from loader.device_frames(device, prefetch=True, data_type=data_type)
         return
@@ -86,8 +87,10 @@ def frames_to_device(loader, data_type, device='cuda'):
         # a movement sequence is shot by one camera: the Morton walk of the rays (shard plan, render order) is computed
         # once per ray count
         key = ('movement', int(ray_index.numel())) if data_type == 'movement' else None
-        yield data, key, {'idx': idx, 'ray_index': ray_index, 'width': int(batch['img_width']),
-                          'height': int(batch['img_height'])}
+        meta = {'idx': idx, 'ray_index': ray_index, 'width': int(batch['img_width']), 'height': int(batch['img_height'])}
+        if 'truth_u8' in batch:          # a derived view of a prepared dataset (views.py): the photograph, for the truth panel
+            meta.update(frame_name=batch['frame_name'], truth_u8=batch['truth_u8'].to(device, non_blocking=True))
+        yield data, key, meta
 
 
 def render_sequence(renderer, loader, data_type, iter_val, on_frame, device='cuda'):

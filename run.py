@@ -1,6 +1,6 @@
 """Render entry point with the reference's command line (run.py:246-247, configs/config.py:65-72):
 
-    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,movement,allview,evaluate} [KEY VALUE ...]
+    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,backview,movement,allview,evaluate} [KEY VALUE ...]
 
 Frames go to experiments/<category>/<task>/<subject>/<experiment>/<load_net>/<folder>/NNNNNN.png
 exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seeded[:N]` renders the
@@ -98,10 +98,14 @@ def _render(data_type, folder_name):
         rgb_img, alpha_img = assemble_uint8_device(meta['width'], meta['height'], meta['ray_index'],
                                                    np.array(cfg.bgcolor) / 255., out['rgb'], out['alpha'],
                                                    want_alpha=bool(cfg.show_alpha))
-        img_dev = torch.cat([rgb_img, alpha_img], dim=1) if cfg.show_alpha else rgb_img
+        # the reference's panel order [rgb, truth, alpha] (run.py:109-116, :177-183); the truth panel is the frame's
+        # photograph as 8-bit pixels, where the loader has one (a prepared dataset; tpose has none)
+        panels = [rgb_img] + ([meta['truth_u8']] if cfg.show_truth and 'truth_u8' in meta else []) + \
+            ([alpha_img] if cfg.show_alpha else [])
+        img_dev = torch.cat(panels, dim=1) if len(panels) > 1 else rgb_img
         # uint8 over PCIe into a pinned staging buffer; the writer thread waits for the copy and encodes the PNG
         # while the next frame renders (nothing here blocks on the GPU)
-        writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type == 'movement' else None)
+        writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type in ('movement', 'backview') else None)
         stats['rays'] += int(meta['ray_index'].numel())
         stats['per_frame'].append(int(meta['ray_index'].numel()))
         stats['frames'] += 1
@@ -146,6 +150,11 @@ def run_freeview():
 
 def run_movement():
     _render('movement', 'movement' if not cfg.render_folder_name else cfg.render_folder_name)
+
+
+def run_backview():
+    """Every frame of the dataset from the camera behind the first frame's (core/data/occnerf/backview.py)."""
+    _render('backview', 'backview' if not cfg.render_folder_name else cfg.render_folder_name)
 
 
 def run_allview():
@@ -193,5 +202,5 @@ def run_evaluate():
 if __name__ == '__main__':
     fn = globals().get(f'run_{args.type}')
     if fn is None:
-        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, movement, allview, evaluate")
+        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, backview, movement, allview, evaluate")
     fn()
