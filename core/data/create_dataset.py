@@ -8,22 +8,24 @@ A prepared dataset directory in the reference's on-disk layout (occnerf_amd/data
 and the SMPL model are not redistributable, tools/make_synthetic_dataset.py writes a stand-in): named by
 `train.dataset_path`, or by the reference's dataset names in `<type>.dataset` as dataset_args.py resolves them
 (zju_<subject>_train -> dataset/zju_mocap/<subject>, monocular_train -> dataset/wild/<cfg.subject>).
-  * 'train': the device-side patch batch loader (PatchBatchLoader; bgcolor None = a random colour per batch,
-    create_dataset.py:31).  Its batches are built on the GPU, so next() needs one;
+  * 'train': the device-side patch batch loader (dataset.loader_from_cfg: PatchBatchLoader; bgcolor None = a random colour
+    per batch, create_dataset.py:31).  Its batches are built on the GPU one step ahead of the optimiser, so next() needs one;
   * 'movement' / 'progress': whole-frame dicts (`ray_shoot_mode 'image'`) with `target_rgbs` and `ray_alpha`, under the
     skip / maxframes rules of create_dataset.py:32-42 (progress: every (total // 16)-th frame, 16 of them; under evaluate
     the first 300; movement under evaluate switches the occlusion band off).  The loader is occnerf_amd.dataset.WholeFrames:
     iterating it gives the host dicts (numpy); sequence.frames_to_device -- run.py, eval.py -- asks it for `device_frames`
-    instead, which builds each frame on the GPU (csrc/frame.hip) one frame ahead of the render;
+    instead, which builds each frame on the GPU (csrc/frame.hip) one frame ahead of the render (occnerf_amd/ahead.py, the
+    one frame-ahead scheme of all three loaders);
   * 'freeview' / 'backview' / 'allview' / 'tpose': the cameras derived from a dataset frame (occnerf_amd.views.ViewFrames,
     the reference's freeview.py / backview.py / allview.py / tpose.py).  Host dicts when iterated; `device_frames` builds
-    the rays on the GPU (csrc/view.hip).  backview reads the directory movement would; allview also needs all_cameras.pkl."""
+    the rays on the GPU (csrc/view.hip), one frame ahead in the same way.  backview reads the directory movement would;
+    allview also needs all_cameras.pkl."""
 import os
 
 import torch
 
 from configs import cfg
-from occnerf_amd.dataset import PatchBatchLoader, PreparedDataset, WholeFrames, resolve_dataset_path
+from occnerf_amd.dataset import PreparedDataset, WholeFrames, loader_from_cfg, resolve_dataset_path
 from occnerf_amd.sequence import SyntheticFrames
 from occnerf_amd.views import KINDS as VIEW_KINDS, ViewFrames
 
@@ -33,11 +35,8 @@ def _prepared(data_type, evaluate, path):
         raise FileNotFoundError(f"dataset directory '{path}' ({data_type}) does not exist")
     device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else None
     if data_type == 'train':
-        ds = PreparedDataset.from_cfg(cfg, path, device=device)
-        return PatchBatchLoader(ds, n_patches=int(cfg.patch.N_patches), size=int(cfg.patch.size),
-                                sample_subject_ratio=float(cfg.patch.sample_subject_ratio), bgcolor=None,
-                                seed=int(dict(cfg.get('train', {})).get('seed', 0)),
-                                prefetch=bool(dict(cfg.get('train', {})).get('prefetch', True)))
+        return loader_from_cfg(cfg, path, device=device, seed=int(dict(cfg.get('train', {})).get('seed', 0)),
+                               prefetch=bool(dict(cfg.get('train', {})).get('prefetch', True)))
     if data_type in VIEW_KINDS:
         return ViewFrames.from_cfg(cfg, path, data_type)
     if data_type not in ('movement', 'progress'):

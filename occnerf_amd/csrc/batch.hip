@@ -171,15 +171,9 @@ __global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8
         out.patch_masks[pix] = hit ? 1 : 0;
         out.row_of_pix[pix] = hit ? row : -1;
         if (hit) {
-            const float *r8 = rays8 + (size_t)p * 8;
+            store_ray_row(rays8 + (size_t)p * 8, row, rmax, out.rays, out.near, out.far);
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
-                out.rays[(int64_t)row * 3 + c] = r8[c];
-                out.rays[(rmax + row) * 3 + c] = r8[3 + c];
-                out.target_rgbs[(int64_t)row * 3 + c] = rgb[c];
-            }
-            out.near[row] = r8[6];
-            out.far[row] = r8[7];
+            for (int c = 0; c < 3; c++) out.target_rgbs[(int64_t)row * 3 + c] = rgb[c];
             out.pix_of_row[row] = (int32_t)pix;
         }
     }

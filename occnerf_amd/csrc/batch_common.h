@@ -1,6 +1,7 @@
-// What the two dataset-frame builders share (batch.hip: the training patch batch; frame.hip: the whole frame): the 256-thread
-// workgroup's reductions and scans, the lane prefix of a wave64 ballot, the reference's float64 blend and its 8-bit
-// quantisation.  One definition of each, so the two builders cannot drift apart.
+// What the three dataset-frame builders share (batch.hip: the training patch batch; frame.hip: the whole frame; view.hip: the
+// rays of a camera without a photograph): the 256-thread workgroup's reductions and scans, the lane prefix of a wave64
+// ballot, the store of one ray row, the reference's float64 blend and its 8-bit quantisation.  One definition of each, so
+// the builders cannot drift apart.
 #pragma once
 
 #include "common.h"
@@ -65,6 +66,19 @@ __device__ __forceinline__ int chunk_rank(bool hit, int *red, int &chunk) {
         chunk += red[w];
     }
     return wave_off + lane_prefix(ballot);
+}
+
+// One ray row from the pixel's entry of rays8 (origin[3], direction[3], near, far): the origin to rays[0][row], the direction
+// to rays[1][row] of rays[2][n_rows][3], near and far to their columns.
+__device__ __forceinline__ void store_ray_row(const float *r8, int64_t row, int64_t n_rows, float *rays, float *near,
+                                              float *far) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        rays[row * 3 + c] = r8[c];
+        rays[(n_rows + row) * 3 + c] = r8[3 + c];
+    }
+    near[row] = r8[6];
+    far[row] = r8[7];
 }
 
 // train.py:296-297, :398 for one channel, in float64 with one rounding per operator (the tree is built with

@@ -85,17 +85,13 @@ __global__ __launch_bounds__(kBatchThreads) void frame_gather_kernel(const uint8
             out.truth_u8[p * 3 + c] = to_8b(rgb[c]);
         }
         if (hit && row < R) {                          // row < R: a caller's R below the scan's total cannot write past the end
-            const float *r8 = rays8 + p * 8;
             out.ray_index[row] = (int64_t)p;
+            store_ray_row(rays8 + p * 8, row, R, out.rays, out.near, out.far);
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-                out.rays[(int64_t)row * 3 + c] = r8[c];
-                out.rays[((int64_t)R + row) * 3 + c] = r8[3 + c];
                 out.target_rgbs[(int64_t)row * 3 + c] = rgb[c];
                 out.ray_alpha[(int64_t)row * 3 + c] = __ddiv_rn((double)m[c], 255.0);
             }
-            out.near[row] = r8[6];
-            out.far[row] = r8[7];
         }
     }
 }

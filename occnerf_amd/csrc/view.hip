@@ -24,15 +24,8 @@ __global__ __launch_bounds__(kBatchThreads) void view_gather_kernel(const float 
         const int row = base + chunk_rank(hit, red, chunk);
         base += chunk;
         if (hit && row < R) {                          // row < R: a caller's R below the scan's total cannot write past the end
-            const float *r8 = rays8 + p * 8;
             ray_index[row] = (int64_t)p;
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-                rays[(int64_t)row * 3 + c] = r8[c];
-                rays[((int64_t)R + row) * 3 + c] = r8[3 + c];
-            }
-            near[row] = r8[6];
-            far[row] = r8[7];
+            store_ray_row(rays8 + p * 8, row, R, rays, near, far);
         }
     }
 }

@@ -4,8 +4,9 @@
 images/NAME.png, masks/NAME.png -- tools/make_synthetic_dataset.py writes one from a seed) and computes, once, everything
 that is constant per frame; the PNGs go to the device once, as uint8.  `PatchBatchLoader` then builds every training batch
 on the device (csrc/batch.hip through ops.patch_batch: four launches with the ray generation), one step ahead of the
-optimiser on a side stream.  The reference builds the same batch in numpy inside two DataLoader workers
-(create_dataset.py:67-72): blend of the whole image in float64, rays of every pixel, box test, one cumulative sum per patch.
+optimiser (ahead.FrameAhead, which `WholeFrames.device_frames` and views.py use for their frames too).  The reference
+builds the same batch in numpy inside two DataLoader workers (create_dataset.py:67-72): blend of the whole image in float64,
+rays of every pixel, box test, one cumulative sum per patch.
 
 What is NOT the reference's, each refused by name where it would matter:
   * a camera with 'distortions' (train.py:290-294 calls cv2.undistort);
@@ -24,6 +25,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .ahead import FrameAhead, cuda_device
 
 WHOLE_FRAME_KEYS = ('rays', 'near', 'far', 'ray_mask', 'bgcolor', 'target_rgbs', 'ray_alpha')
 
@@ -67,22 +69,102 @@ def skeleton_to_bbox(skeleton, bbox_offset):
     return {'min_xyz': np.min(skeleton, axis=0) - bbox_offset, 'max_xyz': np.max(skeleton, axis=0) + bbox_offset}
 
 
-def load_canonical(dataset_path, bbox_offset=0.3, volume_size=32):
-    """What canonical_joints.pkl alone determines (train.py:96-113, :503-535), as the attributes PreparedDataset carries:
-    canonical_joints, avg_betas, canonical_bbox, motion_weights_priors, cnl_gtfms and the three float32 box constants."""
-    with open(os.path.join(dataset_path, 'canonical_joints.pkl'), 'rb') as f:
-        cnl = pickle.load(f)
-    joints = cnl['joints'].astype('float32')
-    bbox = skeleton_to_bbox(joints, bbox_offset)
-    mn, mx = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
-    return {'canonical_joints': joints, 'avg_betas': cnl['avg_betas'].astype('float32'), 'canonical_bbox': bbox,
-            'motion_weights_priors': synth.approx_gaussian_bone_volumes(
-                joints, bbox['min_xyz'], bbox['max_xyz'], grid_size=int(volume_size)).astype('float32'),
-            'cnl_gtfms': synth.get_canonical_global_tfms(joints),
-            'cnl_bbox_min_xyz': mn, 'cnl_bbox_max_xyz': mx, 'cnl_bbox_scale_xyz': 2.0 / (mx - mn)}
+class Subject:
+    """What canonical_joints.pkl alone determines (train.py:96-113, :503-535): canonical_joints, avg_betas, canonical_bbox,
+    motion_weights_priors, cnl_gtfms and the three float32 box constants, on the host and -- after to_device -- on one
+    GPU; and the per-frame constants every loader assembles from them and a pose."""
+
+    def __init__(self, dataset_path, bbox_offset=0.3, volume_size=32):
+        with open(os.path.join(dataset_path, 'canonical_joints.pkl'), 'rb') as f:
+            cnl = pickle.load(f)
+        joints = self.canonical_joints = cnl['joints'].astype('float32')
+        bbox = self.canonical_bbox = skeleton_to_bbox(joints, bbox_offset)
+        self.dataset_path, self.avg_betas = dataset_path, cnl['avg_betas'].astype('float32')
+        self.motion_weights_priors = synth.approx_gaussian_bone_volumes(
+            joints, bbox['min_xyz'], bbox['max_xyz'], grid_size=int(volume_size)).astype('float32')
+        self.cnl_gtfms = synth.get_canonical_global_tfms(joints)
+        self.cnl_bbox_min_xyz, self.cnl_bbox_max_xyz = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
+        self.cnl_bbox_scale_xyz = 2.0 / (self.cnl_bbox_max_xyz - self.cnl_bbox_min_xyz)
+        self.device, self._dev = None, None          # set by to_device
+
+    def upload(self, dev):
+        """What to_device keeps in self._dev."""
+        return {'cnl_gtfms': torch.from_numpy(self.cnl_gtfms).to(dev),
+                'motion_weights_priors': torch.from_numpy(self.motion_weights_priors).to(dev)}
+
+    @staticmethod
+    def upload_pose(pose, dev):
+        return {k: torch.from_numpy(np.ascontiguousarray(pose[k])).to(dev) for k in ('dst_Rs', 'dst_Ts', 'dst_posevec')}
+
+    def to_device(self, device):
+        """Upload once per device; a second call for the same device is free.  -> self."""
+        dev = cuda_device(device, type(self).__name__ + '.to_device', 'the host arrays are self.images / self.alphas')
+        if self._dev is None or self.device != dev:
+            self.device = dev
+            self._dev = self.upload(dev)
+        return self
+
+    def constants(self, pose, device=False):
+        """The reference's per-frame keys that do not depend on the draws (train.py:503-535) for the pose triple `pose`
+        (dst_Rs, dst_Ts, dst_posevec): numpy on the host, or with device=True the tensors to_device and upload_pose made;
+        the three float[3] box constants stay on the host, the kernels take them by value."""
+        gtfms, priors = self.cnl_gtfms, self.motion_weights_priors
+        if device:
+            gtfms, priors = self._dev['cnl_gtfms'], self._dev['motion_weights_priors']
+        return {'dst_Rs': pose['dst_Rs'], 'dst_Ts': pose['dst_Ts'], 'cnl_gtfms': gtfms,
+                'motion_weights_priors': priors, 'cnl_bbox_min_xyz': self.cnl_bbox_min_xyz,
+                'cnl_bbox_max_xyz': self.cnl_bbox_max_xyz, 'cnl_bbox_scale_xyz': self.cnl_bbox_scale_xyz,
+                'dst_posevec': pose['dst_posevec']}
 
 
-class PreparedDataset:
+def host_frame(frame_name, H, W, K, E, box_min, box_max, bgcolor):
+    """What every host frame dict starts with: the rays of an H x W camera that hit the box, as the reference carries them
+    (ray_mask [H*W], rays [2,R,3], near and far [R,1], float32), under the frame's name and size."""
+    rays_o, rays_d = synth.get_rays_from_KRT(H, W, K, E[:3, :3], E[:3, 3])
+    rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3).copy()
+    near, far, ray_mask = synth.rays_intersect_3d_bbox({'min_xyz': box_min, 'max_xyz': box_max}, rays_o, rays_d)
+    return {'frame_name': frame_name, 'img_width': W, 'img_height': H, 'ray_mask': ray_mask,
+            'rays': np.stack([rays_o[ray_mask], rays_d[ray_mask]], 0).astype('float32'),
+            'near': near[:, None].astype('float32'), 'far': far[:, None].astype('float32'), 'bgcolor': bgcolor}
+
+
+def with_batch_dimension(frame):
+    """A host frame dict with the leading batch dimension a DataLoader with batch_size 1 adds (run.py strips it)."""
+    return {k: [v] if isinstance(v, str) else v if np.isscalar(v) else torch.as_tensor(np.asarray(v))[None]
+            for k, v in frame.items()}
+
+
+class CameraRaysAhead:
+    """What WholeFrames.device_frames and ViewFrames.device_frames build ahead (ahead.FrameAhead): the ray of every pixel of
+    an H x W camera and its box test (ops.gen_rays), the hits above every image row (ops.whole_frame_count) and, on the
+    host, their total R.  A buffer set is rays8 [H*W,8], box [H*W] and row_start [H+1]."""
+
+    def __init__(self, device, H, W, prefetch):
+        from . import ops
+        self._ops, self.H, self.W = ops, H, W
+        self._ahead = FrameAhead(device, lambda: {
+            'rays8': torch.empty(H * W, 8, device=device, dtype=torch.float32),
+            'box': torch.empty(H * W, device=device, dtype=torch.uint8),
+            'row_start': torch.empty(H + 1, device=device, dtype=torch.int32)}, host_words=1, prefetch=prefetch)
+
+    def start(self, item, K, E, box_min, box_max):
+        def enqueue(bufs, _item):
+            self._ops.gen_rays(K, E, self.H, self.W, box_min, box_max, self._ahead.device, out=(bufs['rays8'], bufs['box']))
+            self._ops.whole_frame_count(bufs['box'], self.H, self.W, bufs['row_start'])
+            return bufs['row_start'][self.H:]
+        return self._ahead.start(item, enqueue)
+
+    def take(self, ticket):
+        """-> the buffer set, R and start's `item`, a dict with 'frame_name'.  A frame without a ray raises ValueError."""
+        bufs, host, item = self._ahead.take(ticket)
+        R = int(host[0])
+        if R == 0:
+            raise ValueError(f"frame {item['frame_name']}: no ray of its camera hits the box around the body (the box misses "
+                             f'the {self.W} x {self.H} image); nothing to render')
+        return bufs, R, item
+
+
+class PreparedDataset(Subject):
     """A prepared directory, opened once.
 
     The frame list is the sorted PNG names, then [::skip], then [:maxframes] (train.py:68-75).  Per frame, on the host:
@@ -105,7 +187,6 @@ class PreparedDataset:
                  resize_img_scale=1.0, images_prescaled=False, occlude=False, occlusion=None,
                  crop_image_scale=(-1, -1), upsample_pc=False):
         from PIL import Image
-        self.dataset_path, self.device = dataset_path, None if device is None else torch.device(device)
         if not os.path.isdir(os.path.join(dataset_path, 'images')):
             raise FileNotFoundError(f'{dataset_path}: no images/ directory: not a prepared dataset')
         if list(crop_image_scale)[0] != -1:
@@ -125,7 +206,8 @@ class PreparedDataset:
             with open(os.path.join(dataset_path, name), 'rb') as f:
                 return pickle.load(f)
 
-        self.__dict__.update(load_canonical(dataset_path, bbox_offset, volume_size))
+        Subject.__init__(self, dataset_path, bbox_offset, volume_size)
+        self.dataset = self                          # run.py reads loader.dataset.avg_betas
         cameras, mesh_infos = load('cameras.pkl'), load('mesh_infos.pkl')
 
         names = sorted(os.path.splitext(f)[0] for f in os.listdir(os.path.join(dataset_path, 'images'))
@@ -177,30 +259,15 @@ class PreparedDataset:
         self.epoch_frames = [i for i, f in enumerate(self.frames) if not f['empty']]
         if not self.epoch_frames:
             raise ValueError(f'{dataset_path}: every mask is empty (after the occlusion band)')
-        self.dataset = self                          # run.py reads loader.dataset.avg_betas
-        self._dev = None
-        if self.device is not None:
-            self.to_device(self.device)
+        if device is not None:
+            self.to_device(device)
 
-    def to_device(self, device):
-        """Upload the images, the masks (uint8 [H,W,3] each) and the per-frame constants; a second call for the same device
-        is free.  -> self."""
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'PreparedDataset.to_device: {dev} is not a GPU; the host arrays are self.images / self.alphas')
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        if self._dev is not None and self.device == dev:
-            return self
-        self.device = dev
-        self._dev = {
-            'image': [torch.from_numpy(a).to(dev) for a in self.images],
-            'alpha': [torch.from_numpy(a).to(dev) for a in self.alphas],
-            'frame': [{k: torch.from_numpy(np.ascontiguousarray(f[k])).to(dev) for k in ('dst_Rs', 'dst_Ts', 'dst_posevec')}
-                      for f in self.frames],
-            'cnl_gtfms': torch.from_numpy(self.cnl_gtfms).to(dev),
-            'motion_weights_priors': torch.from_numpy(self.motion_weights_priors).to(dev)}
-        return self
+    def upload(self, dev):
+        """The images, the masks (uint8 [H,W,3] each) and the per-frame constants, with the subject's."""
+        return dict(Subject.upload(self, dev),
+                    image=[torch.from_numpy(a).to(dev) for a in self.images],
+                    alpha=[torch.from_numpy(a).to(dev) for a in self.alphas],
+                    frame=[self.upload_pose(f, dev) for f in self.frames])
 
     skeleton_to_bbox = staticmethod(skeleton_to_bbox)
 
@@ -217,21 +284,12 @@ class PreparedDataset:
         return len(self.framelist)
 
     def host_constants(self, i):
-        """The reference's per-frame keys that do not depend on the draws (train.py:503-535), as numpy."""
-        f = self.frames[i]
-        return {'dst_Rs': f['dst_Rs'], 'dst_Ts': f['dst_Ts'], 'cnl_gtfms': self.cnl_gtfms,
-                'motion_weights_priors': self.motion_weights_priors, 'cnl_bbox_min_xyz': self.cnl_bbox_min_xyz,
-                'cnl_bbox_max_xyz': self.cnl_bbox_max_xyz, 'cnl_bbox_scale_xyz': self.cnl_bbox_scale_xyz,
-                'dst_posevec': f['dst_posevec']}
+        """Subject.constants for frame i, as numpy."""
+        return self.constants(self.frames[i])
 
     def device_constants(self, i):
-        """The same on the device (uploaded at open); the three float[3] box constants stay on the host, the kernels take
-        them by value."""
-        d = dict(self._dev['frame'][i])
-        d.update(cnl_gtfms=self._dev['cnl_gtfms'], motion_weights_priors=self._dev['motion_weights_priors'],
-                 cnl_bbox_min_xyz=self.cnl_bbox_min_xyz, cnl_bbox_max_xyz=self.cnl_bbox_max_xyz,
-                 cnl_bbox_scale_xyz=self.cnl_bbox_scale_xyz)
-        return d
+        """The same on the device (uploaded by to_device)."""
+        return self.constants(self._dev['frame'][i], device=True)
 
     def whole_frame(self, i, bgcolor):
         """Frame i as the reference's `ray_shoot_mode 'image'` dict (train.py:353-537 without the patch keys), numpy on the
@@ -241,21 +299,14 @@ class PreparedDataset:
         alpha = self.alphas[i] / 255.
         img = alpha * self.images[i] + (1.0 - alpha) * bg[None, None, :]
         img = (img / 255.).astype('float32')
-        rays_o, rays_d = synth.get_rays_from_KRT(H, W, f['K'], f['E'][:3, :3], f['E'][:3, 3])
-        rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3).copy()
-        near, far, ray_mask = synth.rays_intersect_3d_bbox({'min_xyz': f['dst_bbox_min'], 'max_xyz': f['dst_bbox_max']},
-                                                           rays_o, rays_d)
-        out = {'frame_name': f['frame_name'], 'img_width': W, 'img_height': H, 'ray_mask': ray_mask,
-               'rays': np.stack([rays_o[ray_mask], rays_d[ray_mask]], 0).astype('float32'),
-               'near': near[:, None].astype('float32'), 'far': far[:, None].astype('float32'), 'bgcolor': bg,
-               'target_rgbs': img.reshape(-1, 3)[ray_mask], 'ray_alpha': alpha.reshape(-1, 3)[ray_mask]}
+        out = host_frame(f['frame_name'], H, W, f['K'], f['E'], f['dst_bbox_min'], f['dst_bbox_max'], bg)
+        out.update(target_rgbs=img.reshape(-1, 3)[out['ray_mask']], ray_alpha=alpha.reshape(-1, 3)[out['ray_mask']])
         out.update(self.host_constants(i))
         return out
 
 
 class WholeFrames:
-    """`movement` / `progress` on a prepared dataset: every frame as the whole-frame dict, with the leading batch dimension
-    a DataLoader with batch_size 1 adds (run.py strips it)."""
+    """`movement` / `progress` on a prepared dataset: every frame as the whole-frame dict (with_batch_dimension)."""
 
     def __init__(self, dataset, bgcolor):
         self.dataset, self.bgcolor = dataset, bgcolor
@@ -265,10 +316,7 @@ class WholeFrames:
 
     def __iter__(self):
         for i in range(len(self.dataset)):
-            batch = {}
-            for k, v in self.dataset.whole_frame(i, self.bgcolor).items():
-                batch[k] = [v] if isinstance(v, str) else v if np.isscalar(v) else torch.as_tensor(np.asarray(v))[None]
-            yield batch
+            yield with_batch_dimension(self.dataset.whole_frame(i, self.bgcolor))
 
     def device_frames(self, device, prefetch=True, data_type=None):
         """The same frames built on the device (csrc/frame.hip through ops.whole_frame), as the
@@ -277,59 +325,33 @@ class WholeFrames:
         width, height, frame_name, target_rgbs, ray_alpha and the maps truth_u8 / gt_vis / gt_alpha / body the metrics take.
         Images, masks and per-frame constants are uploaded on first use.
 
-        prefetch=True: the rays, the box test and the row scan of frame t+1 run on a side stream, into the other of two
-        buffer sets, while the consumer renders frame t; its ray count is copied to pinned memory behind an event.  The
-        consumer waits on that event only, makes its stream wait for it and enqueues the gather there: the render stream is
-        never synchronised.  prefetch=False enqueues everything on the current stream and reads the count with one blocking
-        copy.  Both give identical tensors.  data_type 'movement' names the camera for the renderer's ray order, as
-        frames_to_device does.  A frame without a ray raises ValueError."""
+        prefetch=True: the rays, the box test and the row scan of frame t+1 run ahead of the consumer, who renders frame
+        t (CameraRaysAhead); the gather is enqueued on the consumer's stream, which is never synchronised.  prefetch=False
+        enqueues everything on the current stream and reads the count with one blocking copy.  Both give identical
+        tensors.  data_type 'movement' names the camera for the renderer's ray order, as frames_to_device does.  A frame
+        without a ray raises ValueError."""
         from . import ops
         ds = self.dataset.to_device(device)
-        dev, H, W, n = ds.device, ds.height, ds.width, len(ds)
+        H, W, n = ds.height, ds.width, len(ds)
         bg = np.array(self.bgcolor, dtype='float32')
-        sets = [{'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
-                 'box': torch.empty(H * W, device=dev, dtype=torch.uint8),
-                 'row_start': torch.empty(H + 1, device=dev, dtype=torch.int32),
-                 'host': torch.empty(1, dtype=torch.int32).pin_memory(),
-                 'event': torch.cuda.Event()} for _ in range(2 if prefetch else 1)]
-        side = torch.cuda.Stream(device=dev) if prefetch else None
-
-        def enqueue(i):
-            """gen_rays, the count and the copy of R to pinned memory for frame i, on the current stream."""
-            bufs, f = sets[i % len(sets)], ds.frames[i]
-            ops.gen_rays(f['K'], f['E'], H, W, f['dst_bbox_min'], f['dst_bbox_max'], dev, out=(bufs['rays8'], bufs['box']))
-            ops.whole_frame_count(bufs['box'], H, W, bufs['row_start'])
-            bufs['host'].copy_(bufs['row_start'][H:], non_blocking=True)
-            bufs['event'].record()
-            return bufs
+        ahead = CameraRaysAhead(ds.device, H, W, prefetch)
 
         def start(i):
-            if side is None:
-                return enqueue(i)
-            # the buffer set was last read by the gather of frame i - 2, on the consumer's stream
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                return enqueue(i)
+            f = ds.frames[i]
+            return ahead.start(f, f['K'], f['E'], f['dst_bbox_min'], f['dst_bbox_max'])
 
         pending = start(0) if n else None
         for i in range(n):
-            bufs = pending
-            bufs['event'].synchronize()
-            torch.cuda.current_stream(dev).wait_event(bufs['event'])
-            R = int(bufs['host'][0])
-            name = ds.frames[i]['frame_name']
-            if R == 0:
-                raise ValueError(f'frame {name}: no ray of its camera hits the box around the body (the box misses the '
-                                 f'{W} x {H} image); nothing to render')
+            bufs, R, f = ahead.take(pending)
             out = ops.whole_frame(ds._dev['image'][i], ds._dev['alpha'][i], bufs['rays8'], bufs['box'], bg,
                                   row_start=bufs['row_start'], R=R)
             body = bufs['box'].view(H, W).clone()              # the buffer set is rewritten two frames on
-            pending = start(i + 1) if i + 1 < n else None
+            pending = start(i + 1) if i + 1 < n else None      # after the gather is enqueued, before the consumer renders
             data = {'rays': out['rays'], 'near': out['near'], 'far': out['far'], 'bgcolor': torch.from_numpy(bg),
                     'target_rgbs': out['target_rgbs'], 'ray_alpha': out['ray_alpha']}
             data.update({k: (torch.from_numpy(v) if isinstance(v, np.ndarray) else v)
                          for k, v in ds.device_constants(i).items()})
-            meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': name,
+            meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': f['frame_name'],
                     'target_rgbs': out['target_rgbs'], 'ray_alpha': out['ray_alpha'], 'truth_u8': out['truth_u8'],
                     'gt_vis': out['gt_vis'], 'gt_alpha': out['gt_alpha'], 'body': body}
             yield data, ('movement', R) if data_type == 'movement' else None, meta
@@ -342,9 +364,8 @@ class PatchBatchLoader:
     uniforms u[N,2] and -- when `bgcolor` is None, train.py:387-390 -- the background colour (rand(3) * 255 as float32).
     The draws are made in batch order whether or not batches are prefetched, so `prefetch` does not change a batch.
 
-    prefetch=True: batch t+1 is enqueued on a side stream when batch t is handed out, into the other of two buffer sets; its
-    row count and patch_div_indices are copied to pinned memory behind an event, and `next()` waits on that event only, then
-    makes the current stream wait for it.  A batch's tensors are views of its buffer set, which the batch
+    prefetch=True: batch t+1 is built ahead (ahead.FrameAhead) when batch t is handed out; its row count and
+    patch_div_indices come back through pinned memory.  A batch's tensors are views of its buffer set, which the batch
     after the next overwrites: work enqueued on the current stream before the next `next()` reads them safely (the side
     stream waits for it), anything later must copy.  prefetch=False builds the batch in line on the current stream.
 
@@ -360,21 +381,7 @@ class PatchBatchLoader:
             raise ValueError(f'patch.size {self.size} does not fit {dataset.width} x {dataset.height} frames')
         self.bgcolor = None if bgcolor is None else np.array(bgcolor, dtype='float32')
         self.rng, self.prefetch = np.random.RandomState(seed), bool(prefetch)
-        self._sets, self._stream = None, None
-        self._order, self._pending, self._turn = [], None, 0
-
-    def _allocate(self):
-        ds = self.dataset
-        if ds.device is None:
-            raise RuntimeError('PatchBatchLoader: the dataset was opened without a GPU (device=None); the batches are built '
-                               'by HIP kernels, there is no CPU path')
-        dev, H, W = ds.device, ds.height, ds.width
-        self._sets = [{'out': self._ops.alloc_patch_batch(self.n_patches, self.size, H, dev),
-                       'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
-                       'box': torch.empty(H * W, device=dev, dtype=torch.uint8),
-                       'host': torch.empty(self.n_patches + 2, dtype=torch.int32).pin_memory(),
-                       'event': torch.cuda.Event()} for _ in range(2 if self.prefetch else 1)]
-        self._stream = torch.cuda.Stream(device=dev) if self.prefetch else None
+        self._ahead, self._order, self._pending = None, [], None
 
     def __len__(self):
         return len(self.dataset.epoch_frames)
@@ -389,38 +396,35 @@ class PatchBatchLoader:
         bg = (self.rng.rand(3) * 255.).astype('float32') if self.bgcolor is None else self.bgcolor
         return frame, self.rng.rand(self.n_patches, 2), bg
 
-    def _enqueue(self, draw, bufs):
-        """The four launches of one batch and the copy of its counts to pinned memory, on the current stream."""
+    def _enqueue(self, bufs, draw):
+        """The four launches of one batch on the current stream -> what the host reads: patch_div_indices, the row count."""
         frame, u, bg = draw
         ds, f = self.dataset, self.dataset.frames[draw[0]]
         self._ops.gen_rays(f['K'], f['E'], ds.height, ds.width, f['dst_bbox_min'], f['dst_bbox_max'], ds.device,
                            out=(bufs['rays8'], bufs['box']))
         out = self._ops.patch_batch(ds._dev['image'][frame], ds._dev['alpha'][frame], bufs['rays8'], bufs['box'],
                                     self.n_patches, self.size, u, self.ratio, bg, out=bufs['out'])
-        bufs['host'][:self.n_patches + 1].copy_(out['patch_div_indices'], non_blocking=True)
-        bufs['host'][self.n_patches + 1:].copy_(out['n_rows'], non_blocking=True)
-        bufs['event'].record()
-        return draw, bufs
+        return out['patch_div_indices'], out['n_rows']
 
     def _start(self):
-        if self._sets is None:
-            self._allocate()
-        bufs = self._sets[self._turn % len(self._sets)]
-        self._turn += 1
-        draw = self._draw()
-        if self._stream is None:
-            return self._enqueue(draw, bufs)
-        # the buffer set was last read by the step before the previous one, on the consumer's stream
-        self._stream.wait_stream(torch.cuda.current_stream(self.dataset.device))
-        with torch.cuda.stream(self._stream):
-            return self._enqueue(draw, bufs)
+        ds = self.dataset
+        if ds.device is None:
+            raise RuntimeError('PatchBatchLoader: the dataset was opened without a GPU (device=None); the batches are built '
+                               'by HIP kernels, there is no CPU path')
+        if self._ahead is None:                        # the buffers are allocated by the first next()
+            dev, H, W = ds.device, ds.height, ds.width
+            self._ahead = FrameAhead(dev, lambda: {
+                'out': self._ops.alloc_patch_batch(self.n_patches, self.size, H, dev),
+                'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
+                'box': torch.empty(H * W, device=dev, dtype=torch.uint8)},
+                host_words=self.n_patches + 2, prefetch=self.prefetch)
+        return self._ahead.start(self._draw(), self._enqueue)
 
     def __next__(self):
-        (frame, u, bg), bufs = self._pending if self._pending is not None else self._start()
+        ticket = self._pending if self._pending is not None else self._start()
         self._pending = None
-        bufs['event'].synchronize()
-        torch.cuda.current_stream(self.dataset.device).wait_event(bufs['event'])
-        host = bufs['host'].numpy().astype(np.int64)
+        bufs, host, (frame, u, bg) = self._ahead.take(ticket)
+        host = host.numpy().astype(np.int64)
         R, out, ds = int(host[-1]), bufs['out'], self.dataset
         rays = out['rays'][:, :R]
         batch = {'rays': rays if rays.is_contiguous() else rays.contiguous(), 'near': out['near'][:R], 'far': out['far'][:R],
@@ -430,7 +434,7 @@ class PatchBatchLoader:
                  'frame_name': ds.frames[frame]['frame_name'], 'u': u}
         batch.update(ds.device_constants(frame))
         if self.prefetch:
-            self._pending = self._start()
+            self._pending = self._start()              # before the batch is handed out: the consumer's step is not yet enqueued
         return batch
 
     next = __next__

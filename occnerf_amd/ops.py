@@ -1077,6 +1077,30 @@ def whole_frame_count(box_mask, H, W, row_start=None):
     return row_start
 
 
+def _frame_rows(who, H, W, rays8, box_mask, row_start, R, image=None, alpha=None):
+    """What whole_frame and view_frame check alike, under the caller's name, once the caller has refused an H*W out of
+    range in its own words: rays8 / box_mask (and whole_frame's image / alpha) as those of one H x W frame on one device,
+    then row_start and R -- given together, or both None: counted here and read back with one blocking copy.
+    -> (row_start, R, the pointers of (rays8, box_mask, row_start))."""
+    pr, pb = _chk(rays8, torch.float32, 'rays8'), _chk(box_mask, torch.uint8, 'box_mask')
+    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
+        raise RuntimeError(f'{who}: rays8 / box_mask are not those of a {H} x {W} frame')
+    if any(t is not None and t.device != rays8.device for t in (image, alpha, box_mask)):
+        raise RuntimeError(f"{who}: {'rays8' if image is None else 'image, alpha, rays8'} and box_mask must be on one device")
+    if (row_start is None) != (R is None):
+        raise RuntimeError(f'{who}: row_start and R come together (whole_frame_count and its row_start[H])')
+    if row_start is None:
+        row_start = whole_frame_count(box_mask, H, W)
+        R = int(row_start[H].item())
+    R = int(R)
+    ps = _chk(row_start, torch.int32, 'row_start')
+    if row_start.numel() != H + 1 or row_start.device != rays8.device:
+        raise RuntimeError(f'{who}: row_start must be int32 [{H + 1}] on the frame\'s device')
+    if R < 0 or R > H * W:
+        raise RuntimeError(f'{who}: R = {R} is outside [0, {H * W}]')
+    return row_start, R, (pr, pb, ps)
+
+
 def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, out=None):
     """One frame of a prepared dataset as PreparedDataset.whole_frame() builds it on the host, plus the per-pixel maps of the
     metrics (include/occnerf_hip.h occnerf_whole_frame_gather): image / alpha [H,W,3] uint8 on the device, rays8 / box_mask
@@ -1092,22 +1116,7 @@ def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, 
     if H * W >= 1 << 28:
         raise RuntimeError(f'whole_frame: H*W = {H} * {W} must be below 2^28')
     pi, pa = _chk(image, torch.uint8, 'image'), _chk(alpha, torch.uint8, 'alpha')
-    pr, pb = _chk(rays8, torch.float32, 'rays8'), _chk(box_mask, torch.uint8, 'box_mask')
-    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
-        raise RuntimeError(f'whole_frame: rays8 / box_mask are not those of a {H} x {W} frame')
-    if any(t.device != image.device for t in (alpha, rays8, box_mask)):
-        raise RuntimeError('whole_frame: image, alpha, rays8 and box_mask must be on one device')
-    if (row_start is None) != (R is None):
-        raise RuntimeError('whole_frame: row_start and R come together (whole_frame_count and its row_start[H])')
-    if row_start is None:
-        row_start = whole_frame_count(box_mask, H, W)
-        R = int(row_start[H].item())
-    R = int(R)
-    ps = _chk(row_start, torch.int32, 'row_start')
-    if row_start.numel() != H + 1 or row_start.device != image.device:
-        raise RuntimeError(f'whole_frame: row_start must be int32 [{H + 1}] on the frame\'s device')
-    if R < 0 or R > H * W:
-        raise RuntimeError(f'whole_frame: R = {R} is outside [0, {H * W}]')
+    row_start, R, (pr, pb, ps) = _frame_rows('whole_frame', H, W, rays8, box_mask, row_start, R, image, alpha)
     if out is None:
         out = alloc_whole_frame(H, W, R, image.device)
     ptr = {}
@@ -1136,22 +1145,7 @@ def view_frame(rays8, box_mask, H, W, row_start=None, R=None):
     H, W = int(H), int(W)
     if H <= 0 or W <= 0 or H * W >= 1 << 28:
         raise RuntimeError(f'view_frame: H*W = {H} * {W} must be in [1, 2^28)')
-    pr, pb = _chk(rays8, torch.float32, 'rays8'), _chk(box_mask, torch.uint8, 'box_mask')
-    if rays8.numel() != H * W * 8 or box_mask.numel() != H * W:
-        raise RuntimeError(f'view_frame: rays8 / box_mask are not those of a {H} x {W} frame')
-    if rays8.device != box_mask.device:
-        raise RuntimeError('view_frame: rays8 and box_mask must be on one device')
-    if (row_start is None) != (R is None):
-        raise RuntimeError('view_frame: row_start and R come together (whole_frame_count and its row_start[H])')
-    if row_start is None:
-        row_start = whole_frame_count(box_mask, H, W)
-        R = int(row_start[H].item())
-    R = int(R)
-    ps = _chk(row_start, torch.int32, 'row_start')
-    if row_start.numel() != H + 1 or row_start.device != rays8.device:
-        raise RuntimeError(f'view_frame: row_start must be int32 [{H + 1}] on the frame\'s device')
-    if R < 0 or R > H * W:
-        raise RuntimeError(f'view_frame: R = {R} is outside [0, {H * W}]')
+    row_start, R, (pr, pb, ps) = _frame_rows('view_frame', H, W, rays8, box_mask, row_start, R)
     dev = rays8.device
     out = {'ray_index': torch.empty(R, device=dev, dtype=torch.int64), 'rays': torch.empty(2, R, 3, device=dev),
            'near': torch.empty(R, 1, device=dev), 'far': torch.empty(R, 1, device=dev)}

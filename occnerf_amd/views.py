@@ -4,7 +4,7 @@ camera, a box and the pose constants of a dataset frame (tpose: of the canonical
 
 `ViewFrames` yields what dataset.WholeFrames yields: host dicts with the leading batch dimension when iterated, and
 `device_frames` -- (data, key, meta) triples built on the GPU (occnerf_gen_rays, occnerf_whole_frame_count, then
-csrc/view.hip's rays-only row gather through ops.view_frame), one frame ahead of the render on a side stream.
+csrc/view.hip's rays-only row gather through ops.view_frame), one frame ahead of the render (dataset.CameraRaysAhead).
 
   freeview   frame `frame_idx` of the unskipped frame list seen from `render_frames` cameras on an orbit around the body's
              Th (freeview.py:133-142, :197-204); K, box, pose constants and photograph are that frame's;
@@ -26,7 +26,9 @@ import numpy as np
 import torch
 
 from . import synth
-from .dataset import PreparedDataset, apply_global_tfm_to_camera, load_canonical, skeleton_to_bbox
+from .ahead import cuda_device
+from .dataset import (CameraRaysAhead, PreparedDataset, Subject, apply_global_tfm_to_camera, host_frame, skeleton_to_bbox,
+                      with_batch_dimension)
 
 KINDS = ('freeview', 'backview', 'allview', 'tpose')
 ROT_CAM_PARAMS = {'zju_mocap': {'rotate_axis': 'z', 'inv_angle': True},          # freeview.py:25-28
@@ -52,13 +54,12 @@ def src_type_of(cfg, data_type):
     return str(dict(cfg.get('freeview', {}) or {}).get('src_type', 'zju_mocap'))
 
 
-class CanonicalSubject:
-    """What tpose reads of a dataset directory: canonical_joints.pkl (dataset.load_canonical)."""
+class CanonicalSubject(Subject):
+    """What tpose reads of a dataset directory: canonical_joints.pkl (dataset.Subject)."""
 
     def __init__(self, dataset_path, bbox_offset=0.3, volume_size=32):
-        self.dataset_path, self.device, self.bbox_offset = dataset_path, None, float(bbox_offset)
-        self.__dict__.update(load_canonical(dataset_path, bbox_offset, volume_size))
-        self.dataset = self
+        Subject.__init__(self, dataset_path, bbox_offset, volume_size)
+        self.dataset, self.bbox_offset = self, float(bbox_offset)
 
 
 class ViewFrames:
@@ -75,7 +76,8 @@ class ViewFrames:
             raise ValueError(f"ViewFrames: src_type '{src_type}' is none of {tuple(ROT_CAM_PARAMS)}")
         self.dataset, self.kind, self.bgcolor = dataset, kind, np.array(bgcolor, dtype='float32')
         self.src_type, self.period, self.frame_idx = src_type, int(render_frames), int(frame_idx)
-        self._custom, self._dev_custom = {}, {}
+        self._custom = {}                                  # the poses that are no dataset frame's
+        self._uploaded, self._uploaded_to = {}, None       # ... on the device they were last asked for
         if kind == 'tpose':
             self.height = self.width = int(render_size)
             self.total_frames = 1
@@ -183,109 +185,48 @@ class ViewFrames:
         box = self._custom[idx]['bbox'] if idx in self._custom else {'min_xyz': f['dst_bbox_min'], 'max_xyz': f['dst_bbox_max']}
         return {'K': K, 'E': E, 'min': box['min_xyz'], 'max': box['max_xyz'], 'src': src, 'frame_name': f['frame_name']}
 
-    def host_constants(self, idx, src):
-        ds = self.dataset
-        if idx in self._custom:
-            c = self._custom[idx]
-            return {'dst_Rs': c['dst_Rs'], 'dst_Ts': c['dst_Ts'], 'cnl_gtfms': ds.cnl_gtfms,
-                    'motion_weights_priors': ds.motion_weights_priors, 'cnl_bbox_min_xyz': ds.cnl_bbox_min_xyz,
-                    'cnl_bbox_max_xyz': ds.cnl_bbox_max_xyz, 'cnl_bbox_scale_xyz': ds.cnl_bbox_scale_xyz,
-                    'dst_posevec': c['dst_posevec']}
-        return ds.host_constants(src)
-
     def frame(self, idx):
         """Output frame idx as the reference's dict, numpy on the host (freeview.py:177-269 and its siblings)."""
-        v, H, W = self.view(idx), self.height, self.width
-        rays_o, rays_d = synth.get_rays_from_KRT(H, W, v['K'], v['E'][:3, :3], v['E'][:3, 3])
-        rays_o, rays_d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3).copy()
-        near, far, ray_mask = synth.rays_intersect_3d_bbox({'min_xyz': v['min'], 'max_xyz': v['max']}, rays_o, rays_d)
-        out = {'frame_name': v['frame_name'], 'img_width': W, 'img_height': H, 'ray_mask': ray_mask,
-               'rays': np.stack([rays_o[ray_mask], rays_d[ray_mask]], 0).astype('float32'),
-               'near': near[:, None].astype('float32'), 'far': far[:, None].astype('float32'), 'bgcolor': self.bgcolor}
+        v, H, W, ds = self.view(idx), self.height, self.width, self.dataset
+        out = host_frame(v['frame_name'], H, W, v['K'], v['E'], v['min'], v['max'], self.bgcolor)
         if v['src'] is not None:
-            out['truth_u8'] = self.dataset.images[v['src']]
-        out.update(self.host_constants(idx, v['src']))
+            out['truth_u8'] = ds.images[v['src']]
+        out.update(ds.constants(self._custom[idx]) if idx in self._custom else ds.host_constants(v['src']))
         return out
 
     def __iter__(self):
         for i in range(self.total_frames):
-            batch = {}
-            for k, v in self.frame(i).items():
-                batch[k] = [v] if isinstance(v, str) else v if np.isscalar(v) else torch.as_tensor(np.asarray(v))[None]
-            yield batch
-
-    def _device_constants(self, idx, src, dev):
-        """The pose constants of output frame idx on the device; the three float[3] box constants stay on the host."""
-        ds = self.dataset
-        if idx not in self._custom:
-            return ds.device_constants(src)
-        if self._dev_custom.get('device') != dev:
-            self._dev_custom = {'device': dev, 'cnl_gtfms': torch.from_numpy(ds.cnl_gtfms).to(dev),
-                                'motion_weights_priors': torch.from_numpy(ds.motion_weights_priors).to(dev)}
-        if idx not in self._dev_custom:
-            self._dev_custom[idx] = {k: torch.from_numpy(np.ascontiguousarray(self._custom[idx][k])).to(dev)
-                                     for k in ('dst_Rs', 'dst_Ts', 'dst_posevec')}
-        d = dict(self._dev_custom[idx])
-        d.update(cnl_gtfms=self._dev_custom['cnl_gtfms'], motion_weights_priors=self._dev_custom['motion_weights_priors'],
-                 cnl_bbox_min_xyz=ds.cnl_bbox_min_xyz, cnl_bbox_max_xyz=ds.cnl_bbox_max_xyz,
-                 cnl_bbox_scale_xyz=ds.cnl_bbox_scale_xyz)
-        return d
+            yield with_batch_dimension(self.frame(i))
 
     def device_frames(self, device, prefetch=True, data_type=None):
         """The same frames built on the device, as the (data, key, meta) triples
         sequence.frames_to_device yields: `data` holds what Network.forward takes, as device tensors (the float[3] constants
         on the host); `meta` holds idx, ray_index, width, height, frame_name and, where the frame has a photograph, truth_u8:
         the resident uint8 image itself.  The scheme is WholeFrames.device_frames': with prefetch the rays, the box test and
-        the row scan of frame t+1 run on a side stream into the other of two buffer sets and its ray count is copied to
-        pinned memory behind an event; the consumer waits on that event only.  prefetch=False enqueues everything on the
-        current stream.  Both give identical tensors.  The ray-order key is None: the camera changes every frame.  A frame
-        without a ray raises ValueError."""
+        the row scan of frame t+1 run ahead of the consumer (dataset.CameraRaysAhead); prefetch=False enqueues everything
+        on the current stream.  Both give identical tensors.  The ray-order key is None: the camera changes every frame.
+        A frame without a ray raises ValueError."""
         from . import ops
-        dev = torch.device(device)
-        if dev.type != 'cuda':
-            raise RuntimeError(f'ViewFrames.device_frames: {dev} is not a GPU; iterate the loader for the host frames')
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        ds = self.dataset if self.kind == 'tpose' else self.dataset.to_device(dev)
+        dev = cuda_device(device, 'ViewFrames.device_frames', 'iterate the loader for the host frames')
+        ds = self.dataset.to_device(dev)                   # a CanonicalSubject uploads its two tensors, a dataset its frames
         H, W, n = self.height, self.width, self.total_frames
-        sets = [{'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
-                 'box': torch.empty(H * W, device=dev, dtype=torch.uint8),
-                 'row_start': torch.empty(H + 1, device=dev, dtype=torch.int32),
-                 'host': torch.empty(1, dtype=torch.int32).pin_memory(),
-                 'event': torch.cuda.Event()} for _ in range(2 if prefetch else 1)]
-        side = torch.cuda.Stream(device=dev) if prefetch else None
-
-        def enqueue(i):
-            """gen_rays, the count and the copy of R to pinned memory for frame i, on the current stream."""
-            bufs, v = sets[i % len(sets)], self.view(i)
-            ops.gen_rays(v['K'], v['E'], H, W, v['min'], v['max'], dev, out=(bufs['rays8'], bufs['box']))
-            ops.whole_frame_count(bufs['box'], H, W, bufs['row_start'])
-            bufs['host'].copy_(bufs['row_start'][H:], non_blocking=True)
-            bufs['event'].record()
-            return bufs, v
+        ahead = CameraRaysAhead(dev, H, W, prefetch)
+        if self._uploaded_to != dev:                       # once per device, kept over calls
+            self._uploaded = {i: ds.upload_pose(pose, dev) for i, pose in self._custom.items()}
+            self._uploaded_to = dev
 
         def start(i):
-            if side is None:
-                return enqueue(i)
-            # the buffer set was last read by the gather of frame i - 2, on the consumer's stream
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                return enqueue(i)
+            v = self.view(i)
+            return ahead.start(v, v['K'], v['E'], v['min'], v['max'])
 
         pending = start(0) if n else None
         for i in range(n):
-            bufs, v = pending
-            bufs['event'].synchronize()
-            torch.cuda.current_stream(dev).wait_event(bufs['event'])
-            R = int(bufs['host'][0])
-            if R == 0:
-                raise ValueError(f"frame {v['frame_name']}: no ray of its camera hits the box around the body (the box misses "
-                                 f'the {W} x {H} image); nothing to render')
+            bufs, R, v = ahead.take(pending)
             out = ops.view_frame(bufs['rays8'], bufs['box'], H, W, row_start=bufs['row_start'], R=R)
-            pending = start(i + 1) if i + 1 < n else None
+            pending = start(i + 1) if i + 1 < n else None  # after the gather is enqueued, before the consumer renders
             data = {'rays': out['rays'], 'near': out['near'], 'far': out['far'], 'bgcolor': torch.from_numpy(self.bgcolor)}
-            data.update({k: (torch.from_numpy(c) if isinstance(c, np.ndarray) else c)
-                         for k, c in self._device_constants(i, v['src'], dev).items()})
+            consts = ds.constants(self._uploaded[i], device=True) if i in self._custom else ds.device_constants(v['src'])
+            data.update({k: (torch.from_numpy(c) if isinstance(c, np.ndarray) else c) for k, c in consts.items()})
             meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': v['frame_name']}
             if v['src'] is not None:
                 meta['truth_u8'] = ds._dev['image'][v['src']]
