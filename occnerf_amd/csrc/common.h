@@ -51,6 +51,24 @@ __device__ __forceinline__ T ld32(const T *base, uint32_t byte_off) {
     return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + byte_off);
 }
 
+// ReLU of a value produced by an MFMA or other arithmetic (an accumulator, a sum with a bias) in ONE instruction,
+// v_med3_f32 y, x, +inf, 0.  fmaxf(x, 0.0f) compiles to two -- `v_max_f32 t, x, x` quiets a possible signalling NaN before
+// `v_max_f32 y, 0, t` -- and beside fp32 MFMAs every VALU instruction costs matrix time.  A signalling NaN cannot reach this
+// helper: arithmetic instructions (MFMA, add, fma) only ever produce quiet NaNs, so the first of the two is the identity on
+// every value that arrives here.  The median returns the bits of the second: x for x > 0 (+inf included), +0 for every
+// x < 0 and for both zeros (with +inf the largest of the three the instruction returns v_max_f32(x, 0)), and, as it returns
+// v_min3_f32 when an operand is a NaN, 0 for a quiet NaN.  Do not use it on values loaded from memory.
+// Why not inline assembly (`v_max_f32 y, 0, x`): the compiler does not place the wait states a VALU read of a register
+// needs after the MFMA that wrote it when the reader is an asm statement -- measured: the 32x32 direct-load non-rigid kernel
+// came out 4e-5 wrong.  v_med3_f32 is an instruction the hazard recogniser knows, and the scheduler stays free to move it.
+// The bound comes from a (hoisted) scalar move the optimiser cannot see through: with a literal +inf it folds the median
+// back into fmaxf and its two instructions.
+__device__ __forceinline__ float relu_arith(float x) {
+    float inf;
+    asm("s_mov_b32 %0, 0x7f800000" : "=s"(inf));
+    return __builtin_amdgcn_fmed3f(x, 0.0f, inf);
+}
+
 // ---- multi-resolution grid: per-level constants computed on the HOST so that device
 // exp2f accuracy never enters the result (oracle: oc_grid_level_params) ---------------
 constexpr int kMaxLevels = 16;

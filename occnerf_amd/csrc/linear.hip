@@ -107,7 +107,7 @@ __device__ __forceinline__ f32x4 out_quad(const f32x16 (&acc)[NB], int nb, int q
     for (int j = 0; j < 4; j++) v[j] = acc[nb][4 * q + j] + b[j];
     if (a.relu) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) v[j] = fmaxf(v[j], 0.0f);
+        for (int j = 0; j < 4; j++) v[j] = relu_arith(v[j]);
     }
     if (a.aux && m < a.M && a.aux_col >= n && a.aux_col < n + 4) {
 #pragma unroll

@@ -144,7 +144,7 @@ __device__ __forceinline__ void relu_into(f32x4 (&act)[kOB], const f32x4 (&acc)[
 #pragma unroll
     for (int ob = 0; ob < kOB; ob++) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) act[ob][r] = fmaxf(acc[ob][r], 0.0f);
+        for (int r = 0; r < 4; r++) act[ob][r] = relu_arith(acc[ob][r]);
     }
 }
 

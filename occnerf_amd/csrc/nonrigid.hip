@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void nonrigid_kernel(const float *xyz_in /*
 #define BOP_SKIP(t) ((t) < 64 ? act[((t) >> 4) & 3][(t) & 15] : e[((t) - 64) < 0 ? 0 : ((t) - 64)])
 #define NR_RELU()                                                                     \
     _Pragma("unroll") for (int ob = 0; ob < kNrOB; ob++) {                            \
-        _Pragma("unroll") for (int r = 0; r < 16; r++) act[ob][r] = fmaxf(acc[ob][r], 0.0f); \
+        _Pragma("unroll") for (int r = 0; r < 16; r++) act[ob][r] = relu_arith(acc[ob][r]); \
     }
     nr_load_bias(acc, pk + NrBlob::kL0B, h);
     NR_LAYER(kG_E, NrBlob::kL0W * 4, acc, BOP_E)

@@ -247,7 +247,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
 #define NR16_RELU()                                                                              \
     _Pragma("unroll") for (int T_ = 0; T_ < 2; T_++) {                                           \
         _Pragma("unroll") for (int ob_ = 0; ob_ < kOB; ob_++) {                                  \
-            _Pragma("unroll") for (int r_ = 0; r_ < 4; r_++) act[T_][ob_][r_] = fmaxf(acc[T_][ob_][r_], 0.0f); \
+            _Pragma("unroll") for (int r_ = 0; r_ < 4; r_++) act[T_][ob_][r_] = relu_arith(acc[T_][ob_][r_]); \
         }                                                                                        \
     }
 

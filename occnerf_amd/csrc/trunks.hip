@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
 #pragma unroll
             for (int sub = 0; sub < 2; sub++) {
 #pragma unroll
-                for (int i = 0; i < 8; i++) b[ob * 2 + sub][i] = (__bf16)fmaxf(acc_[ob][sub * 8 + i], 0.0f);
+                for (int i = 0; i < 8; i++) b[ob * 2 + sub][i] = (__bf16)relu_arith(acc_[ob][sub * 8 + i]);
             }
         }
 #ifdef OCC_TRUNKS_EXP_NO_SAVE      // (tools/trunks_phases.py: what the kernel costs without writing the activations)
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
             for (int q = 0; q < 4; q++) {
                 const f32x4 w = W4[(kb * 4 + q) * 2 + h];
 #pragma unroll
-                for (int rr = 0; rr < 4; rr++) sacc = __fmaf_rn(w[rr], fmaxf(acc[kb][q * 4 + rr], 0.0f), sacc);
+                for (int rr = 0; rr < 4; rr++) sacc = __fmaf_rn(w[rr], relu_arith(acc[kb][q * 4 + rr]), sacc);
             }
         }
         sigma = (sacc + __shfl_xor(sacc, 32)) + aux[Aux::kSigma + 256];
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
             for (int q = 0; q < 4; q++) {
                 const f32x4 w = W4[(kb * 4 + q) * 2 + h];
 #pragma unroll
-                for (int rr = 0; rr < 4; rr++) sacc = __fmaf_rn(w[rr], fmaxf(acc[kb][q * 4 + rr], 0.0f), sacc);
+                for (int rr = 0; rr < 4; rr++) sacc = __fmaf_rn(w[rr], relu_arith(acc[kb][q * 4 + rr]), sacc);
             }
         }
         rgb[c] = (sacc + __shfl_xor(sacc, 32)) + aux[Aux::kOut + 3 * kWidth + c];
