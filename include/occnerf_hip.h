@@ -726,6 +726,22 @@ int occnerf_frame_metrics(const uint8_t *pred, const uint8_t *truth, const float
                           const float *gt_vis_alpha, const float *gt_alpha, int32_t N, int32_t H, int32_t W,
                           double data_range, double *record, double *ssim_map, void *workspace, void *stream);
 
+/* One frame of the trainer's progress dump (the reference's trainer.py:346-383) written into its tile of the mosaic:
+ * the rendered panel -- uint8(255 * clip(x, 0, 1)) of the ray's colour where ray_index[R] (int64, ascending flat pixel index)
+ * has the pixel, of h_bgcolor01[3] (HOST, float32(cfg.bgcolor / 255)) elsewhere, exactly occnerf_assemble_image's bytes --
+ * to mosaic pixel (tile_y * H + y, tile_x * 2W + x) and truth_u8[H,W,3] to (tile_y * H + y, tile_x * 2W + W + x).
+ * mosaic: uint8 [mosaic_rows, mosaic_cols, 3] (sizes in pixels); a tile that does not fit is refused, and no byte outside
+ * the tile's H x 2W rectangle is written.  *off_bg (one int32 on the device) = the number of the H*W*3 rendered bytes v with
+ * |v - b| > 3 + 1e-5 |b| in fp64, b = h_bgcolor255[3] (HOST, double, cfg.bgcolor as given): 0 exactly when
+ * np.allclose(rendered, cfg.bgcolor, atol=3.) holds.  partial: occnerf_progress_tile_blocks(H, W) int32 of workspace (-1 for
+ * sizes that are refused: H * W must be below 2^28).  R = 0 is legal (rgb and ray_index may then be NULL): the rendered
+ * panel is all background.  Two launches, no atomics, no host wait. */
+int32_t occnerf_progress_tile_blocks(int32_t height, int32_t width);
+int occnerf_progress_tile(const float *rgb, const int64_t *ray_index, int64_t R, int32_t height, int32_t width,
+                          const float *h_bgcolor01, const double *h_bgcolor255, const uint8_t *truth_u8, uint8_t *mosaic,
+                          int32_t mosaic_rows, int32_t mosaic_cols, int32_t tile_x, int32_t tile_y, int32_t *partial,
+                          int32_t *off_bg, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

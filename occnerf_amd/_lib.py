@@ -137,6 +137,8 @@ SIGNATURES = {
     'occnerf_view_frame_gather': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     'occnerf_frame_metrics_workspace_bytes': (_i64, [_i32, _i32, _i32]),
     'occnerf_frame_metrics': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
+    'occnerf_progress_tile_blocks': (_i32, [_i32, _i32]),
+    'occnerf_progress_tile': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -94,7 +94,12 @@ _DEFAULTS = {
     # already at the training size (only K is scaled; nothing is resized here)
     # train.seed: the loader's host RNG (frame order, patch draws, background colours); train.prefetch: build batch t+1 on a
     # side stream while step t runs
-    'train': {'dataset_path': None, 'images_prescaled': False, 'seed': 0, 'prefetch': True},
+    # train.save_checkpt_interval / save_model_interval, save_all, progress.dump_interval: the reference's checkpoint and
+    # progress-dump schedule (occnerf_amd/trainer.py; its default.yaml:93-94, :106, :145); progress.dump_interval 0: no dumps.
+    # `resume True` continues from <load_net>.tar in the logdir (`latest` where load_net names the seeded checkpoint)
+    'train': {'dataset_path': None, 'images_prescaled': False, 'seed': 0, 'prefetch': True,
+              'save_checkpt_interval': 2000, 'save_model_interval': 40000},
+    'progress': {'dump_interval': 500}, 'save_all': True,
     # the simulated occlusion of the reference's training set (core/data/occnerf/train.py:286-287): the mask columns
     # [mid - width // 2, mid + width // 2) of the first `range` frames of the frame list are zeroed
     'occlude': False, 'occlusion': {'range': 405, 'mid': 451, 'width': 86},

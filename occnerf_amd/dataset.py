@@ -357,6 +357,18 @@ class WholeFrames:
             yield data, ('movement', R) if data_type == 'movement' else None, meta
 
 
+def pack_random_state(rng):
+    """numpy RandomState -> plain tensors and numbers (the trainer's resume sidecar loads without unpickling numpy objects)."""
+    kind, key, pos, has_gauss, cached = rng.get_state()
+    return {'kind': str(kind), 'key': torch.from_numpy(np.asarray(key, dtype=np.int64).copy()), 'pos': int(pos),
+            'has_gauss': int(has_gauss), 'cached_gaussian': float(cached)}
+
+
+def unpack_random_state(rng, st):
+    rng.set_state((st['kind'], st['key'].numpy().astype(np.uint32), int(st['pos']), int(st['has_gauss']),
+                   float(st['cached_gaussian'])))
+
+
 class PatchBatchLoader:
     """The training batches of a PreparedDataset, built on the device.
 
@@ -381,7 +393,7 @@ class PatchBatchLoader:
             raise ValueError(f'patch.size {self.size} does not fit {dataset.width} x {dataset.height} frames')
         self.bgcolor = None if bgcolor is None else np.array(bgcolor, dtype='float32')
         self.rng, self.prefetch = np.random.RandomState(seed), bool(prefetch)
-        self._ahead, self._order, self._pending = None, [], None
+        self._ahead, self._order, self._pending, self._before_draw = None, [], None, None
 
     def __len__(self):
         return len(self.dataset.epoch_frames)
@@ -390,11 +402,41 @@ class PatchBatchLoader:
         return self
 
     def _draw(self):
+        self._before_draw = (self.rng.get_state(), list(self._order))
         if not self._order:
             self._order = [self.dataset.epoch_frames[j] for j in self.rng.permutation(len(self.dataset.epoch_frames))]
         frame = self._order.pop(0)
         bg = (self.rng.rand(3) * 255.).astype('float32') if self.bgcolor is None else self.bgcolor
         return frame, self.rng.rand(self.n_patches, 2), bg
+
+    def state(self):
+        """The host generator and the rest of the epoch as of the NEXT batch this loader hands out: with a batch built ahead,
+        the state before its draws, so that a loader restored from it (load_state) draws that batch again and none twice.
+        Plain tensors and numbers (the trainer's resume sidecar, occnerf_amd/trainer.py)."""
+        if self._pending is not None:
+            rng = np.random.RandomState()
+            rng.set_state(self._before_draw[0])
+            return dict(pack_random_state(rng), order=[int(i) for i in self._before_draw[1]])
+        return dict(pack_random_state(self.rng), order=[int(i) for i in self._order])
+
+    def load_state(self, st):
+        """Continue from state(): a batch that was built ahead is dropped, its draws are made again."""
+        self._drop_pending()
+        unpack_random_state(self.rng, st)
+        self._order = [int(i) for i in st['order']]
+
+    def reseed(self, seed):
+        """A fresh stream and a fresh epoch (a resume that has no recorded state)."""
+        self._drop_pending()
+        self.rng.seed(int(seed))
+        self._order = []
+
+    def _drop_pending(self):
+        """Take the batch that is being built ahead and discard it: the next start() then finds no build in flight in the
+        buffer set it rotates onto."""
+        if self._pending is not None:
+            self._ahead.take(self._pending)
+            self._pending = None
 
     def _enqueue(self, bufs, draw):
         """The four launches of one batch on the current stream -> what the host reads: patch_div_indices, the row count."""
