@@ -38,7 +38,7 @@ def _prepared(data_type, evaluate, path):
         return loader_from_cfg(cfg, path, device=device, seed=int(dict(cfg.get('train', {})).get('seed', 0)),
                                prefetch=bool(dict(cfg.get('train', {})).get('prefetch', True)))
     if data_type in VIEW_KINDS:
-        return ViewFrames.from_cfg(cfg, path, data_type)
+        return ViewFrames.from_cfg(cfg, path, data_type, prepare_device=device)
     if data_type not in ('movement', 'progress'):
         raise NotImplementedError(f"type '{data_type}' on the prepared dataset '{path}': train, movement, progress, "
                                   'freeview, backview, allview and tpose read a dataset')
@@ -48,7 +48,8 @@ def _prepared(data_type, evaluate, path):
         skip, maxframes = (1, 300) if evaluate else (max(total // 16, 1), 16)
     if data_type == 'movement' and evaluate:
         cfg.occlude = False
-    return WholeFrames(PreparedDataset.from_cfg(cfg, path, device=None, skip=skip, maxframes=maxframes), cfg.bgcolor)
+    return WholeFrames(PreparedDataset.from_cfg(cfg, path, device=None, skip=skip, maxframes=maxframes, prepare_device=device),
+                       cfg.bgcolor)
 
 
 def create_dataloader(data_type='train', evaluate=False, **_):

@@ -706,6 +706,22 @@ int occnerf_whole_frame_gather(const uint8_t *image, const uint8_t *alpha, const
 int occnerf_view_frame_gather(const float *rays8, const uint8_t *box_mask, int32_t H, int32_t W, const int32_t *row_start,
                               int32_t R, int64_t *ray_index, float *rays, float *near, float *far, void *stream);
 
+/* A photograph (and its mask) undistorted when a prepared dataset is opened: the reference's cv2.undistort(img, K, D) lines
+ * (core/data/occnerf/train.py:290-294, allview.py:166-170) as occnerf_amd/undistort.py's undistort_u8 defines them -- OpenCV's
+ * undistort -> initUndistortRectifyMap (CV_16SC2 maps, 1/32-pixel fractions) -> remap (INTER_LINEAR, BORDER_CONSTANT 0) with
+ * the camera matrix kept, stated as a pure function of the inputs (equality with a particular OpenCV
+ * build is not claimed).  image[H,W,3] uint8 on the device; mask[H,W,3] uint8 or NULL (then out_mask is NULL too); HOST
+ * h_K[9] (the 3x3 camera matrix as stored, row-major, K[0,1] = 0) and h_dist[8] = (k1, k2, p1, p2, k3, k4, k5, k6), missing
+ * coefficients 0, both double.  For every pixel (win_y + r, win_x + c) of the window the source position (u, v) is computed in
+ * fp64 with one rounding per operator, quantised to rint(32 u), rint(32 v) (ties to even, saturated to int32; a non-finite
+ * position gives 0), and the four taps around it are blended with integer weights that sum to 1024, a tap outside the image
+ * reading 0: out = (acc + 512) >> 10 -> out_image[win_h,win_w,3], out_mask[win_h,win_w,3], which must not overlap the inputs.
+ * The map is always that of the full image; only the window is written.  One launch, one thread per window pixel, six
+ * channels from one map.  H * W < 2^28; the window lies inside the image.  No atomics, no host wait; bit-identical to numpy. */
+int occnerf_undistort_u8(const uint8_t *image, const uint8_t *mask, int32_t H, int32_t W, const double *h_K,
+                         const double *h_dist, int32_t win_y, int32_t win_x, int32_t win_h, int32_t win_w,
+                         uint8_t *out_image, uint8_t *out_mask, void *stream);
+
 /* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
  * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
  * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance

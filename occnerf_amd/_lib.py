@@ -135,6 +135,7 @@ SIGNATURES = {
     'occnerf_whole_frame_count': (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     'occnerf_whole_frame_gather': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32] + [_vp] * 9 + [_vp]),
     'occnerf_view_frame_gather': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'occnerf_undistort_u8': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'occnerf_frame_metrics_workspace_bytes': (_i64, [_i32, _i32, _i32]),
     'occnerf_frame_metrics': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     'occnerf_progress_tile_blocks': (_i32, [_i32, _i32]),

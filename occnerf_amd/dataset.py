@@ -8,14 +8,23 @@ optimiser (ahead.FrameAhead, which `WholeFrames.device_frames` and views.py use 
 builds the same batch in numpy inside two DataLoader workers (create_dataset.py:67-72): blend of the whole image in float64,
 rays of every pixel, box test, one cumulative sum per patch.
 
+Frames are PREPARED at open when `prepare_frames` is set (PreparedDataset.from_cfg sets it unless `train.prepare_frames False`
+is configured), in the reference's order (train.py:286-304): the occlusion band on the raw mask, then image and mask
+undistorted with the frame's own 'intrinsics' / 'distortions' (:290-294; undistort.undistort_u8 on the host,
+csrc/undistort.hip through ops.undistort_u8 with a device -- DESIGN.md section 7f), then the crop_image_scale window
+(:300-304, with K's principal point as :422-427 sets it).  A prepared photograph is again a uint8 photograph, so everything
+downstream reads the 6-byte-per-pixel resident frame as before.  Without `prepare_frames` (the constructor's default) such
+a dataset is refused by name.
+
 What is NOT the reference's, each refused by name where it would matter:
-  * a camera with 'distortions' (train.py:290-294 calls cv2.undistort);
-  * crop_image_scale other than [-1, -1] (:300-304, :422-427);
   * upsample_pc (:384-385, needs trimesh and the SMPL faces);
   * resize_img_scale != 1 on PNGs that are not already at the training size.  The reference blends at full size and then
     resizes the float image with cv2's Lanczos filter and the mask with its bilinear one (:306-314); neither filter nor that
     order exists here, so nothing is resized: with `train.images_prescaled True` the PNGs are taken to BE the training images
-    (resized by the user, any filter) and only K[:2] is scaled (:430); otherwise the scale is refused;
+    (resized by the user, any filter) and only K[:2] is scaled (:430); otherwise the scale is refused.  Prescaled PNGs no
+    longer match the stored K, so 'distortions' or a crop together with a scale other than 1 are refused too.  Resizing
+    needs float-resident frames and is the next step;
+  * 12 or 14 distortion coefficients (OpenCV's thin prism and tilt models) and a skewed camera matrix;
   * the 'verts' key (:381, :416): it needs an SMPL model and Network.forward does not read it.
 """
 import os
@@ -25,6 +34,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .undistort import undistort_u8
 from .ahead import FrameAhead, cuda_device
 
 WHOLE_FRAME_KEYS = ('rays', 'near', 'far', 'ray_mask', 'bgcolor', 'target_rgbs', 'ray_alpha')
@@ -63,6 +73,18 @@ def occlusion_columns(occlusion, W):
     """The mask columns train.py:286-287 zeroes: [mid - width // 2, mid + width // 2) as a python slice of W columns."""
     mid, width = int(occlusion['mid']), int(occlusion['width'])
     return slice(mid - width // 2, mid + width // 2).indices(W)[:2]
+
+
+def crop_window(crop, H, W):
+    """The window (y0, x0, h, w) of train.py:300-304: img[mid_x - dx//2 : mid_x + (dx - dx//2), mid_y - dy//2 : mid_y +
+    (dy - dy//2)] with mid_x, mid_y = H // 2, W // 2 and dx, dy = crop_image_scale -- dx counts rows.  A crop that does not
+    lie inside the image is a ValueError (numpy would silently clip or wrap the slice)."""
+    dx, dy = int(crop[0]), int(crop[1])
+    y0, x0 = H // 2 - dx // 2, W // 2 - dy // 2
+    if dx <= 0 or dy <= 0 or y0 < 0 or x0 < 0 or y0 + dx > H or x0 + dy > W:
+        raise ValueError(f'crop_image_scale={[dx, dy]}: a crop of {dx} rows x {dy} columns does not lie inside the '
+                         f'{W} x {H} image')
+    return y0, x0, dx, dy
 
 
 def skeleton_to_bbox(skeleton, bbox_offset):
@@ -181,15 +203,22 @@ class PreparedDataset(Subject):
     reference's `while np.sum(alpha) < 1` test (:395): the reference returns a RANDOM OTHER frame in its place (:396), so
     its epoch keeps its length and shows some frame twice; here the epoch is shorter instead.
 
+    prepare_frames=True undistorts and crops every frame at open (the module docstring): a camera with 'distortions' and
+    a crop_image_scale other than [-1, -1] are then opened instead of refused; `height`, `width`, `empty` and K are those of
+    the prepared frame.  With a `device` the kernel does the work and the prepared pair is copied back once per frame, so
+    `self.images` / `self.alphas` (whole_frame(), views.py) hold prepared frames on either route, identical ones.
+    prepare_device: the GPU that prepares the frames of a dataset that itself stays on the host (device=None).
+
     device=None keeps everything on the host (the host constants can be checked without a GPU)."""
 
     def __init__(self, dataset_path, device='cuda:0', skip=1, maxframes=-1, bbox_offset=0.3, volume_size=32,
                  resize_img_scale=1.0, images_prescaled=False, occlude=False, occlusion=None,
-                 crop_image_scale=(-1, -1), upsample_pc=False):
+                 crop_image_scale=(-1, -1), upsample_pc=False, prepare_frames=False, prepare_device=None):
         from PIL import Image
         if not os.path.isdir(os.path.join(dataset_path, 'images')):
             raise FileNotFoundError(f'{dataset_path}: no images/ directory: not a prepared dataset')
-        if list(crop_image_scale)[0] != -1:
+        crop = None if list(crop_image_scale)[0] == -1 else tuple(int(v) for v in crop_image_scale)
+        if crop is not None and not prepare_frames:
             raise NotImplementedError(f'crop_image_scale={list(crop_image_scale)}: cropping (train.py:300-304) is not built; '
                                       'only [-1, -1]')
         if upsample_pc:
@@ -201,6 +230,13 @@ class PreparedDataset(Subject):
                 f'resize_img_scale={scale}: the reference resizes the blended image with cv2 (train.py:306-314), which is not '
                 'available. Resize the PNGs yourself and set train.images_prescaled True (K is then scaled, the PNGs are '
                 'not), or set resize_img_scale 1')
+        if scale != 1.0 and crop is not None:
+            raise NotImplementedError(f'crop_image_scale={list(crop)} with resize_img_scale={scale}: the crop (train.py:300-304) '
+                                      'is in pixels of the full-size image, which prescaled PNGs no longer are')
+        if prepare_device is None:
+            prepare_device = device
+        if prepare_frames and prepare_device is not None:
+            prepare_device = cuda_device(prepare_device, 'PreparedDataset', 'device=None prepares the frames on the host')
 
         def load(name):
             with open(os.path.join(dataset_path, name), 'rb') as f:
@@ -218,30 +254,45 @@ class PreparedDataset(Subject):
         if not names:
             raise FileNotFoundError(f'{dataset_path}/images holds no PNG')
         self.framelist, self.occlude = names, bool(occlude)
-        self.frames, self.images, self.alphas = [], [], []
+        self.frames, self.images, self.alphas, raw_size = [], [], [], None
         for idx, name in enumerate(names):
             if name not in cameras:
                 raise KeyError(f'{dataset_path}/cameras.pkl has no camera for frame {name}')
-            if 'distortions' in cameras[name]:
+            distorted = 'distortions' in cameras[name]
+            if distorted and not prepare_frames:
                 raise NotImplementedError(f"frame {name}: the camera has 'distortions'; undistorting the image "
                                           '(train.py:290-294, cv2.undistort) is not built. Undistort the PNGs and drop the key')
+            if distorted and scale != 1.0:
+                raise NotImplementedError(f"frame {name}: the camera has 'distortions' and resize_img_scale is {scale}: "
+                                          'prescaled PNGs no longer match the stored intrinsics, so they cannot be undistorted')
             img = np.array(Image.open(os.path.join(dataset_path, 'images', name + '.png')).convert('RGB'))
             alpha = np.array(Image.open(os.path.join(dataset_path, 'masks', name + '.png')).convert('RGB'))
             if alpha.shape != img.shape:
                 raise ValueError(f'frame {name}: image is {img.shape}, mask is {alpha.shape}')
-            if self.frames and img.shape[:2] != (self.height, self.width):
+            if self.frames and img.shape[:2] != raw_size:
                 raise ValueError(f'frame {name}: {img.shape[1]} x {img.shape[0]} pixels, the first frame has '
-                                 f'{self.width} x {self.height}: one resident ray buffer serves every frame')
-            self.height, self.width = int(img.shape[0]), int(img.shape[1])
+                                 f'{raw_size[1]} x {raw_size[0]}: one resident ray buffer serves every frame')
+            raw_size = img.shape[:2]
             band = self.occlude and idx < int(occlusion['range'])
-            if band:
-                c0, c1 = occlusion_columns(occlusion, self.width)
+            if band:                                 # on the raw mask, before it is undistorted (:286-287, then :290-294)
+                c0, c1 = occlusion_columns(occlusion, raw_size[1])
                 alpha[:, c0:c1] = 0
+            window = None if crop is None else crop_window(crop, *raw_size)
+            if distorted:
+                img, alpha = self._undistorted(img, alpha, cameras[name], window, prepare_device)
+            elif window is not None:
+                y0, x0, h, w = window
+                img, alpha = img[y0:y0 + h, x0:x0 + w], alpha[y0:y0 + h, x0:x0 + w]
+            self.height, self.width = int(img.shape[0]), int(img.shape[1])
             info = mesh_infos[name]
             poses = info['poses'].astype('float32')
             joints = info['joints'].astype('float32')
             bbox = self.skeleton_to_bbox(info['joints'], bbox_offset)        # on the pickle's own dtype, as :130 does
             K = np.array(cameras[name]['intrinsics'])[:3, :3].copy()
+            if crop is not None:
+                # :422-427 to the letter: dx is the crop's ROW extent (img[mid_x - dx//2 : ...] slices rows) and yet it sets
+                # cx, the principal point's COLUMN; dy, the column extent, sets cy.  The original principal point is dropped.
+                K[0, 2], K[1, 2] = crop[0] / 2, crop[1] / 2
             K[:2] *= scale
             Rh, Th = info['Rh'].astype('float32'), info['Th'].astype('float32')
             E = apply_global_tfm_to_camera(np.asarray(cameras[name]['extrinsics']), Rh, Th)
@@ -262,6 +313,18 @@ class PreparedDataset(Subject):
         if device is not None:
             self.to_device(device)
 
+    @staticmethod
+    def _undistorted(img, alpha, cam, window, device):
+        """Image and (banded) mask of one frame undistorted with the frame's own camera, the window only: numpy on the host,
+        or with a device one launch on it and one copy back."""
+        K, D = cam['intrinsics'], cam['distortions']
+        if device is None:
+            return undistort_u8(img, K, D, window), undistort_u8(alpha, K, D, window)
+        from . import ops
+        pair = ops.undistort_u8(torch.from_numpy(np.ascontiguousarray(img)).to(device),
+                                torch.from_numpy(np.ascontiguousarray(alpha)).to(device), K, D, window)
+        return pair[0].cpu().numpy(), pair[1].cpu().numpy()
+
     def upload(self, dev):
         """The images, the masks (uint8 [H,W,3] each) and the per-frame constants, with the subject's."""
         return dict(Subject.upload(self, dev),
@@ -272,13 +335,18 @@ class PreparedDataset(Subject):
     skeleton_to_bbox = staticmethod(skeleton_to_bbox)
 
     @classmethod
-    def from_cfg(cls, cfg, dataset_path, device='cuda:0', skip=1, maxframes=-1):
+    def from_cfg(cls, cfg, dataset_path, device='cuda:0', skip=1, maxframes=-1, crop_image_scale=None, prepare_device=None):
+        """The dataset as the configuration describes it; frames are prepared (undistorted, cropped) unless
+        `train.prepare_frames False`.  crop_image_scale: in the place of the configured one (views.py: [-1, -1]);
+        prepare_device: as the constructor's."""
         tr = dict(cfg.get('train', {}) or {})
+        crop = cfg.get('crop_image_scale', [-1, -1]) if crop_image_scale is None else crop_image_scale
         return cls(dataset_path, device=device, skip=skip, maxframes=maxframes, bbox_offset=float(cfg.bbox_offset),
                    volume_size=int(cfg.mweight_volume.volume_size), resize_img_scale=float(cfg.resize_img_scale),
                    images_prescaled=bool(tr.get('images_prescaled', False)), occlude=cfg.get('occlude', False) is True,
-                   occlusion=cfg.get('occlusion'), crop_image_scale=cfg.get('crop_image_scale', [-1, -1]),
-                   upsample_pc=bool(cfg.get('upsample_pc', False)))
+                   occlusion=cfg.get('occlusion'), crop_image_scale=crop,
+                   upsample_pc=bool(cfg.get('upsample_pc', False)), prepare_frames=bool(tr.get('prepare_frames', True)),
+                   prepare_device=prepare_device)
 
     def __len__(self):
         return len(self.framelist)

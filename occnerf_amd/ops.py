@@ -1154,3 +1154,35 @@ def view_frame(rays8, box_mask, H, W, row_start=None, R=None):
                                                   out['near'].data_ptr(), out['far'].data_ptr(), _stream(rays8))
     _lib.check(rc, 'view_frame_gather')
     return out
+
+
+# ------------------------------------------------------------------ undistorting a frame at open
+def undistort_u8(image, mask, K, D, window=None, out=None):
+    """occnerf_amd.undistort.undistort_u8 on the device (include/occnerf_hip.h occnerf_undistort_u8): image [H,W,3] uint8 and
+    mask [H,W,3] uint8 or None on one device, K the 3x3 camera matrix as stored and D 4 / 5 / 8 coefficients on the host,
+    window (y0, x0, h, w) or None for the whole image -> (image', mask' or None), uint8 [h,w,3], on the current stream.
+    out: the pair to fill in place (the second entry None without a mask); it must not share memory with the inputs."""
+    from . import undistort as und
+    if not torch.is_tensor(image) or image.dim() != 3 or image.shape[2] != 3:
+        raise RuntimeError('undistort_u8: image must be a [H,W,3] tensor')
+    H, W = int(image.shape[0]), int(image.shape[1])
+    if H * W >= 1 << 28:
+        raise RuntimeError(f'undistort_u8: H*W = {H} * {W} must be below 2^28')
+    pi, pm = _chk(image, torch.uint8, 'image'), _opt(mask, torch.uint8, 'mask')
+    if mask is not None and (tuple(mask.shape) != (H, W, 3) or mask.device != image.device):
+        raise RuntimeError(f'undistort_u8: mask must be [{H},{W},3] on the device of image')
+    k, d = und.camera(K).reshape(9), und.coefficients(D)
+    y0, x0, h, w = und.check_window(window, H, W)
+    if out is None:
+        out = (torch.empty(h, w, 3, device=image.device, dtype=torch.uint8),
+               None if mask is None else torch.empty(h, w, 3, device=image.device, dtype=torch.uint8))
+    oi, om = out
+    if (om is None) != (mask is None):
+        raise RuntimeError('undistort_u8: out holds a mask exactly when a mask is given')
+    po, pom = _chk(oi, torch.uint8, 'out image'), _opt(om, torch.uint8, 'out mask')
+    if any(t is not None and (tuple(t.shape) != (h, w, 3) or t.device != image.device) for t in (oi, om)):
+        raise RuntimeError(f'undistort_u8: out must be [{h},{w},3] on the device of image')
+    with _guard(image):
+        rc = _lib.lib().occnerf_undistort_u8(pi, pm, H, W, k.ctypes.data, d.ctypes.data, y0, x0, h, w, po, pom, _stream(image))
+    _lib.check(rc, 'undistort_u8')
+    return oi, om

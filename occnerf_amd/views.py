@@ -18,7 +18,12 @@ csrc/view.hip's rays-only row gather through ops.view_frame), one frame ahead of
              synth.setup_camera(render_size) (tpose.py:50-84, :133-205); no photograph.
 
 `truth_u8` (host dict and meta) is the resident uint8 photograph itself: the reference shows to_8b_image(img / 255.) as its
-truth panel (freeview.py:187, :234), which maps each of the 256 grey levels to itself."""
+truth panel (freeview.py:187, :234), which maps each of the 256 grey levels to itself.  The resident photograph is the
+PREPARED one: from_cfg opens the dataset with prepare_frames (dataset.py), so a frame whose camera has 'distortions' is
+undistorted with that camera (freeview.py:156, backview.py:159); these loaders have no crop code, so nothing is cropped.
+An allview rig with 'distortions' undistorts the RAW photograph of the source frame with rig camera idx's own K and D for
+every output frame (allview.py:166-170): the raw photograph is kept, and the truth panel of frame idx is
+undistort.undistort_u8 of it on the host, csrc/undistort.hip's on the device."""
 import os
 import pickle
 
@@ -26,6 +31,7 @@ import numpy as np
 import torch
 
 from . import synth
+from .undistort import undistort_u8
 from .ahead import cuda_device
 from .dataset import (CameraRaysAhead, PreparedDataset, Subject, apply_global_tfm_to_camera, host_frame, skeleton_to_bbox,
                       with_batch_dimension)
@@ -66,16 +72,19 @@ class ViewFrames:
     """dataset: a PreparedDataset opened with skip 1 and all frames (tpose: a CanonicalSubject will do).  bgcolor in 0..255.
     src_type, render_frames, frame_idx: see the module docstring; render_size: tpose's image side; bbox_offset: the box
     margin of the bodies of all_mesh_infos.pkl (the dataset's own boxes are already built); skip / maxframes: backview's
-    frame list, the reference's framelist[::skip][:maxframes]."""
+    frame list, the reference's framelist[::skip][:maxframes].  truth: False leaves the truth panel of an allview rig with
+    'distortions' out (it costs an undistortion per output frame); every other panel is the resident photograph and is
+    always handed over."""
 
     def __init__(self, dataset, kind, bgcolor=(255., 255., 255.), src_type='zju_mocap', render_frames=100, frame_idx=0,
-                 render_size=512, bbox_offset=0.3, skip=1, maxframes=-1):
+                 render_size=512, bbox_offset=0.3, skip=1, maxframes=-1, truth=True):
         if kind not in KINDS:
             raise ValueError(f"ViewFrames: kind '{kind}' is none of {KINDS}")
         if kind != 'tpose' and src_type not in ROT_CAM_PARAMS:
             raise ValueError(f"ViewFrames: src_type '{src_type}' is none of {tuple(ROT_CAM_PARAMS)}")
         self.dataset, self.kind, self.bgcolor = dataset, kind, np.array(bgcolor, dtype='float32')
         self.src_type, self.period, self.frame_idx = src_type, int(render_frames), int(frame_idx)
+        self.truth, self._D, self._raw, self._raw_dev = bool(truth), None, None, None
         self._custom = {}                                  # the poses that are no dataset frame's
         self._uploaded, self._uploaded_to = {}, None       # ... on the device they were last asked for
         if kind == 'tpose':
@@ -115,13 +124,24 @@ class ViewFrames:
         name = ds.framelist[self.frame_idx]
         if name not in cams:
             raise KeyError(f'{path} has no cameras for frame {name}')
-        if 'distortions' in cams[name]:
-            raise NotImplementedError(f"{path}, frame {name}: the cameras have 'distortions'; undistorting the image "
-                                      '(allview.py:166-170, cv2.undistort) is not built')
         self._K, self._E = np.asarray(cams[name]['intrinsics']), np.asarray(cams[name]['extrinsics'])
         if self._K.shape[0] < self.total_frames or self._E.shape[0] < self.total_frames:
             raise ValueError(f'{path}: frame {name} has {min(self._K.shape[0], self._E.shape[0])} cameras, allview renders '
                              f'{self.total_frames}')
+        if 'distortions' in cams[name]:                    # allview.py:166-170: the raw photograph, rig camera idx's K and D
+            from PIL import Image
+            if ds.resize_img_scale != 1.0:
+                raise NotImplementedError(f"{path}, frame {name}: the cameras have 'distortions' and resize_img_scale is "
+                                          f'{ds.resize_img_scale}: prescaled PNGs no longer match the stored intrinsics')
+            self._D = np.asarray(cams[name]['distortions'], dtype=np.float64)
+            if self._D.shape[0] < self.total_frames:
+                raise ValueError(f"{path}: frame {name} has {self._D.shape[0]} 'distortions', allview renders "
+                                 f'{self.total_frames}')
+            self._raw = np.ascontiguousarray(np.array(
+                Image.open(os.path.join(ds.dataset_path, 'images', name + '.png')).convert('RGB')))
+            if self._raw.shape != (ds.height, ds.width, 3):
+                raise ValueError(f'{path}: the raw photograph of frame {name} is {self._raw.shape[1]} x {self._raw.shape[0]}, '
+                                 f'the opened dataset has {ds.width} x {ds.height} (allview does not crop)')
         mesh = os.path.join(ds.dataset_path, 'all_mesh_infos.pkl')
         self._all_mesh = None
         if os.path.isfile(mesh):                           # has_all_mesh: the body is given per camera
@@ -138,15 +158,19 @@ class ViewFrames:
                                    'bbox': skeleton_to_bbox(info['joints'][c], bbox_offset)}
 
     @classmethod
-    def from_cfg(cls, cfg, dataset_path, kind):
-        """create_dataloader(kind) on a prepared directory.  PreparedDataset's refusals apply unchanged."""
+    def from_cfg(cls, cfg, dataset_path, kind, prepare_device=None):
+        """create_dataloader(kind) on a prepared directory.  The dataset is opened as PreparedDataset.from_cfg opens it
+        (frames undistorted), without a crop: the reference's freeview / backview / allview loaders have no crop code.  The
+        truth panel of a distorted allview rig is built only under `show_truth`.  prepare_device: the GPU that undistorts
+        the frames at open (None: numpy on the host)."""
         common = dict(bgcolor=cfg.bgcolor, src_type=src_type_of(cfg, kind), render_frames=int(cfg.render_frames),
                       frame_idx=int(cfg.freeview.get('frame_idx', 0)), render_size=int(cfg.get('render_size', 512)),
-                      bbox_offset=float(cfg.bbox_offset))
+                      bbox_offset=float(cfg.bbox_offset), truth=bool(cfg.get('show_truth', False)))
         if kind == 'tpose':
             return cls(CanonicalSubject(dataset_path, float(cfg.bbox_offset), int(cfg.mweight_volume.volume_size)), kind,
                        **common)
-        return cls(PreparedDataset.from_cfg(cfg, dataset_path, device=None, skip=1, maxframes=-1), kind, **common)
+        return cls(PreparedDataset.from_cfg(cfg, dataset_path, device=None, skip=1, maxframes=-1, crop_image_scale=[-1, -1],
+                                            prepare_device=prepare_device), kind, **common)
 
     def __len__(self):
         return self.total_frames
@@ -189,8 +213,10 @@ class ViewFrames:
         """Output frame idx as the reference's dict, numpy on the host (freeview.py:177-269 and its siblings)."""
         v, H, W, ds = self.view(idx), self.height, self.width, self.dataset
         out = host_frame(v['frame_name'], H, W, v['K'], v['E'], v['min'], v['max'], self.bgcolor)
-        if v['src'] is not None:
+        if v['src'] is not None and self._D is None:
             out['truth_u8'] = ds.images[v['src']]
+        elif v['src'] is not None and self.truth:
+            out['truth_u8'] = undistort_u8(self._raw, self._K[idx], self._D[idx])
         out.update(ds.constants(self._custom[idx]) if idx in self._custom else ds.host_constants(v['src']))
         return out
 
@@ -202,9 +228,9 @@ class ViewFrames:
         """The same frames built on the device, as the (data, key, meta) triples
         sequence.frames_to_device yields: `data` holds what Network.forward takes, as device tensors (the float[3] constants
         on the host); `meta` holds idx, ray_index, width, height, frame_name and, where the frame has a photograph, truth_u8:
-        the resident uint8 image itself.  The scheme is WholeFrames.device_frames': with prefetch the rays, the box test and
-        the row scan of frame t+1 run ahead of the consumer (dataset.CameraRaysAhead); prefetch=False enqueues everything
-        on the current stream.  Both give identical tensors.  The ray-order key is None: the camera changes every frame.
+        the resident uint8 image itself (a distorted allview rig: the raw photograph undistorted for the frame's camera).
+        The scheme is WholeFrames.device_frames': with prefetch the rays, the box test and the row scan of frame t+1 run
+        ahead of the consumer (dataset.CameraRaysAhead); prefetch=False enqueues everything on the current stream.  Both give identical tensors.  The ray-order key is None: the camera changes every frame.
         A frame without a ray raises ValueError."""
         from . import ops
         dev = cuda_device(device, 'ViewFrames.device_frames', 'iterate the loader for the host frames')
@@ -213,6 +239,7 @@ class ViewFrames:
         ahead = CameraRaysAhead(dev, H, W, prefetch)
         if self._uploaded_to != dev:                       # once per device, kept over calls
             self._uploaded = {i: ds.upload_pose(pose, dev) for i, pose in self._custom.items()}
+            self._raw_dev = None if self._raw is None else torch.from_numpy(self._raw).to(dev)
             self._uploaded_to = dev
 
         def start(i):
@@ -228,6 +255,8 @@ class ViewFrames:
             consts = ds.constants(self._uploaded[i], device=True) if i in self._custom else ds.device_constants(v['src'])
             data.update({k: (torch.from_numpy(c) if isinstance(c, np.ndarray) else c) for k, c in consts.items()})
             meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': v['frame_name']}
-            if v['src'] is not None:
+            if v['src'] is not None and self._D is None:
                 meta['truth_u8'] = ds._dev['image'][v['src']]
+            elif v['src'] is not None and self.truth:      # on the consumer's stream, like the gather
+                meta['truth_u8'] = ops.undistort_u8(self._raw_dev, None, self._K[i], self._D[i])[0]
             yield data, None, meta

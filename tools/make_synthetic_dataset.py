@@ -2,13 +2,14 @@
 from a seed: the SMPL model is licensed and the ZJU-MoCap / OcMotion pickles are not redistributable, so this is the
 stand-in a user -- and the tests -- can train on.
 
-    python tools/make_synthetic_dataset.py OUT_DIR [--frames 8 --width 512 --height 512 --seed 0 --all-cameras 0]
+    python tools/make_synthetic_dataset.py OUT_DIR [--frames 8 --width 512 --height 512 --seed 0 --all-cameras 0
+                                                    --distortions k1,k2,p1,p2[,k3[,k4,k5,k6]]]
 
-    OUT_DIR/cameras.pkl            {frame: {'intrinsics' 3x3, 'extrinsics' 4x4}}                       float64
+    OUT_DIR/cameras.pkl            {frame: {'intrinsics' 3x3, 'extrinsics' 4x4[, 'distortions' n]}}    float64
     OUT_DIR/mesh_infos.pkl         {frame: {'poses' 72, 'betas' 10, 'tpose_joints' 24x3, 'joints' 24x3, 'Rh' 3, 'Th' 3}}
     OUT_DIR/canonical_joints.pkl   {'joints' 24x3, 'avg_betas' 10}
     OUT_DIR/images/NAME.png, OUT_DIR/masks/NAME.png        NAME = frame_%06d (train.py:358 parses the six digits)
-    OUT_DIR/all_cameras.pkl        {frame: {'intrinsics' Nx3x3, 'extrinsics' Nx4x4}}     float64; only with --all-cameras N > 0:
+    OUT_DIR/all_cameras.pkl        {frame: {'intrinsics' Nx3x3, 'extrinsics' Nx4x4[, 'distortions' Nxn]}}     float64; only with --all-cameras N > 0:
                                    the rig `--type allview` renders from (allview.py:92-96), a ring of N cameras around the body
 
 The subject is occnerf_amd/synth.py's capsule body walking between two seeded poses (synth.movement_pose), each vertex
@@ -18,7 +19,11 @@ loader has to apply apply_global_tfm_to_camera (camera_util.py:113-130) to find 
 posed vertex is projected and splatted as a disc, far to near (the nearest vertex ends on top), coloured by a fixed function
 of the vertex's CANONICAL position, so the views agree with one another; the mask is the discs' coverage with an
 anti-aliased rim, i.e. it holds fractional values, not only 0 and 255.  The background of the image is seeded noise: only
-the blend with the mask removes it.  Same arguments, same bytes in every array and pixel."""
+the blend with the mask removes it.  Same arguments, same bytes in every array and pixel.
+
+With --distortions the cameras carry the coefficients (OpenCV's order) and every photograph and mask is what a lens with those
+coefficients would have recorded of the clean one (lens_image), so a loader has to undistort them (core/data/occnerf/
+train.py:290-294) to see the body where the cameras put it."""
 import argparse
 import os
 import pickle
@@ -86,6 +91,37 @@ def paint(uv, depth, radius_px, colours, H, W, background):
     return img, np.round(cover * 255.0).astype(np.uint8)
 
 
+def lens_image(clean, K, dist):
+    """What a lens with the coefficients dist = (k1, k2, p1, p2[, k3[, k4, k5, k6]]) records of the clean image (uint8 [H,W] or
+    [H,W,C]) of camera K: every recorded pixel is a DISTORTED position; the ideal position that the model sends there is
+    found by fixed-point iteration (20 rounds of x <- (xd - tangential(x)) / radial(x), OpenCV's undistortPoints), and the
+    clean image is sampled there bilinearly, zero outside."""
+    d = np.zeros(8)
+    d[:len(dist)] = np.asarray(dist, dtype=np.float64).ravel()
+    k1, k2, p1, p2, k3, k4, k5, k6 = d
+    H, W = clean.shape[:2]
+    xd = ((np.arange(W, dtype=np.float64) - K[0, 2]) / K[0, 0])[None, :] + np.zeros((H, 1))
+    yd = ((np.arange(H, dtype=np.float64) - K[1, 2]) / K[1, 1])[:, None] + np.zeros((1, W))
+    x, y = xd.copy(), yd.copy()
+    for _ in range(20):
+        r2 = x * x + y * y
+        inv = (1 + ((k6 * r2 + k5) * r2 + k4) * r2) / (1 + ((k3 * r2 + k2) * r2 + k1) * r2)
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x, y = (xd - dx) * inv, (yd - dy) * inv
+    u, v = K[0, 0] * x + K[0, 2], K[1, 1] * y + K[1, 2]
+    u, v = np.clip(np.nan_to_num(u, nan=-2.0), -2.0, W + 1.0), np.clip(np.nan_to_num(v, nan=-2.0), -2.0, H + 1.0)
+    x0, y0 = np.floor(u).astype(np.int64), np.floor(v).astype(np.int64)
+    a, b = u - x0, v - y0
+    src = np.zeros((H + 2, W + 2) + clean.shape[2:], dtype=np.float64)
+    src[1:-1, 1:-1] = clean
+    if clean.ndim == 3:
+        a, b = a[..., None], b[..., None]
+    xa, xb, ya, yb = (np.clip(t, -1, n) + 1 for t, n in ((x0, W), (x0 + 1, W), (y0, H), (y0 + 1, H)))
+    out = (1 - b) * ((1 - a) * src[ya, xa] + a * src[ya, xb]) + b * ((1 - a) * src[yb, xa] + a * src[yb, xb])
+    return np.round(out).astype(np.uint8)
+
+
 def frame_camera(i, frames, H, W, focal):
     K32, E32 = synth.setup_camera(max(H, W), focal=focal)
     E = E32.astype(np.float64)
@@ -104,11 +140,16 @@ def camera_ring(K, E, Th, n):
     return {'intrinsics': np.repeat(K[None], n, axis=0), 'extrinsics': np.stack(Es, 0)}
 
 
-def make_dataset(out_dir, frames=8, width=512, height=512, seed=0, focal=1250.0, all_cameras=0):
+def make_dataset(out_dir, frames=8, width=512, height=512, seed=0, focal=1250.0, all_cameras=0, distortions=None):
     """Write the directory; -> the list of frame names.  all_cameras=N > 0 also writes all_cameras.pkl (camera_ring); with
-    0 the directory is exactly what it is without the argument."""
+    0 the directory is exactly what it is without the argument.  distortions: 4, 5 or 8 lens coefficients, written into
+    both camera files, and every photograph and mask as that lens records it (lens_image); None changes nothing."""
     from PIL import Image
     H, W = int(height), int(width)
+    if distortions is not None:
+        distortions = np.asarray(distortions, dtype=np.float64).ravel()
+        if distortions.size not in (4, 5, 8):
+            raise ValueError(f'distortions: {distortions.size} coefficients; 4, 5 or 8 (k1, k2, p1, p2[, k3[, k4, k5, k6]])')
     rng = np.random.RandomState(seed)
     betas = np.zeros(10, dtype='float32')
     tjoints = synth.tpose_joints(betas)
@@ -133,11 +174,17 @@ def make_dataset(out_dir, frames=8, width=512, height=512, seed=0, focal=1250.0,
         radius = np.maximum(DISC_RADIUS_M * K[0, 0] / depth, MIN_DISC_PX)
         background = rng.randint(0, 256, size=(H, W, 3)).astype(np.uint8)
         img, mask = paint(uv, depth, radius, colours, H, W, background)
+        if distortions is not None:
+            img, mask = lens_image(img, K, distortions), lens_image(mask, K, distortions)
         Image.fromarray(img, 'RGB').save(os.path.join(out_dir, 'images', name + '.png'))
         Image.fromarray(mask, 'L').save(os.path.join(out_dir, 'masks', name + '.png'))
         cameras[name] = {'intrinsics': K, 'extrinsics': E}
         if int(all_cameras) > 0:
             rigs[name] = camera_ring(K, E, Th, int(all_cameras))
+        if distortions is not None:
+            cameras[name]['distortions'] = distortions.copy()
+            if int(all_cameras) > 0:
+                rigs[name]['distortions'] = np.repeat(distortions[None], int(all_cameras), axis=0)
         mesh_infos[name] = {'poses': pose.astype('float32'), 'betas': betas.copy(),
                             'tpose_joints': tjoints.astype('float32'), 'joints': joints.astype('float32'), 'Rh': Rh, 'Th': Th}
         names.append(name)
@@ -161,8 +208,11 @@ def main():
     ap.add_argument('--focal', type=float, default=1250.0, help='focal length at 512 pixels (scaled with the larger side)')
     ap.add_argument('--all-cameras', type=int, default=0, help='N > 0: also write all_cameras.pkl, a ring of N cameras '
                                                                'around the body for every frame (--type allview)')
+    ap.add_argument('--distortions', type=lambda t: [float(v) for v in t.split(',')], default=None,
+                    help='k1,k2,p1,p2[,k3[,k4,k5,k6]]: the cameras carry these lens coefficients and the photographs and '
+                         'masks are recorded through that lens')
     a = ap.parse_args()
-    names = make_dataset(a.out_dir, a.frames, a.width, a.height, a.seed, a.focal, a.all_cameras)
+    names = make_dataset(a.out_dir, a.frames, a.width, a.height, a.seed, a.focal, a.all_cameras, a.distortions)
     print(f'wrote {len(names)} frames of {a.width} x {a.height} to {a.out_dir}')
 
 
