@@ -101,7 +101,7 @@ def eval_model(render_folder_name='eval', show_truth=True, show_alpha=True):
                 m, imgs = metrics.frame_metrics_from_maps(out['rgb'], out['alpha'], ray_index, meta, W, H, bgcolor=bg,
                                                           with_images=True)
             elif on_dataset:                                    # host frames (`device_frames False`)
-                gt_alpha = torch.from_numpy((loader.dataset.alphas[meta['idx']][:, :, 0] / 255.).astype('float32')).to(dev)
+                gt_alpha = torch.from_numpy(loader.dataset.gt_alpha(meta['idx'])).to(dev)
                 m, imgs = metrics.frame_metrics(out['rgb'], out['alpha'], ray_index, data['target_rgbs'], W, H,
                                                 ray_alpha=data['ray_alpha'], gt_alpha=gt_alpha, bgcolor=bg, with_images=True)
             else:

@@ -722,6 +722,42 @@ int occnerf_undistort_u8(const uint8_t *image, const uint8_t *mask, int32_t H, i
                          const double *h_dist, int32_t win_y, int32_t win_x, int32_t win_h, int32_t win_w,
                          uint8_t *out_image, uint8_t *out_mask, void *stream);
 
+/* A prepared frame resized to the training size: the reference's two cv2.resize lines (core/data/occnerf/train.py:306-314) as
+ * occnerf_amd/resize.py's resize_blend defines them (equality with a particular OpenCV build is not
+ * claimed).  image[H,W,3] uint8 or NULL (then img64 is NULL too: the mask alone), mask[H,W,3] uint8, on the device; HOST
+ * h_bgcolor[3] in 0..255 (may be NULL without an image).  The tables are resize.py's resize_tables of both axes and both
+ * filters, on the device: x_off_lanczos[w,8] / y_off_lanczos[h,8] int32 clamped source columns / rows with their float32
+ * weights x_w_lanczos / y_w_lanczos, and x_off_bilinear[w,2] ... y_w_bilinear[h,2].  h_*_off_*: HOST copies of the four
+ * offset tables, which are checked before anything is launched -- an offset outside the image, or y offsets that do not
+ * ascend or span more than 24 source rows for one output row, are refused by name.
+ * img64[h,w,3] fp64 = the eight-tap Lanczos resize of the float64 blend (m / 255.) * image + (1.0 - m / 255.) * bgcolor (NOT
+ * divided by 255, not clipped: it leaves [0, 255] at edges), alpha64[h,w,3] fp64 = the bilinear resize of m / 255.  Both
+ * passes are left-to-right sums from 0.0 of double(source) * double(weight), one rounding per operator, the horizontal pass
+ * first.  The outputs must not overlap the inputs.  H * W and h * w < 2^28.  One launch: a workgroup computes the horizontal
+ * sums of its 32 output columns once into LDS and runs the vertical pass from there.  No atomics, no host wait;
+ * bit-identical to numpy. */
+int occnerf_resize_frame(const uint8_t *image, const uint8_t *mask, int32_t H, int32_t W, int32_t h, int32_t w,
+                         const int32_t *x_off_lanczos, const float *x_w_lanczos, const int32_t *y_off_lanczos,
+                         const float *y_w_lanczos, const int32_t *x_off_bilinear, const float *x_w_bilinear,
+                         const int32_t *y_off_bilinear, const float *y_w_bilinear, const int32_t *h_x_off_lanczos,
+                         const int32_t *h_y_off_lanczos, const int32_t *h_x_off_bilinear, const int32_t *h_y_off_bilinear,
+                         const float *h_bgcolor, double *img64, double *alpha64, void *stream);
+
+/* occnerf_patch_batch and occnerf_whole_frame_gather on a frame occnerf_resize_frame has written: img64[H,W,3] and
+ * alpha64[H,W,3] fp64 in the place of image and alpha, H x W the training size.  The same kernels with another pixel source:
+ * a subject pixel is alpha64[p,0] > 0, the target float32(img64 / 255.) (the background is already blended in; h_bgcolor
+ * still colours truth_u8 outside the box), ray_alpha = alpha64, gt_alpha = float32(alpha64[p,0]), gt_vis that value inside
+ * the box and 0 outside.  Everything else as documented for the uint8 entries. */
+int occnerf_patch_batch_f64(const double *img64, const double *alpha64, const float *rays8, const uint8_t *box_mask,
+                            int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u, double subject_ratio,
+                            const float *h_bgcolor, int32_t *row_counts, float *rays, float *near, float *far,
+                            float *target_rgbs, float *target_patches, uint8_t *patch_masks, int32_t *patch_div_indices,
+                            int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix, int32_t *n_rows, void *stream);
+int occnerf_whole_frame_gather_f64(const double *img64, const double *alpha64, const float *rays8, const uint8_t *box_mask,
+                                   int32_t H, int32_t W, const float *h_bgcolor, const int32_t *row_start, int32_t R,
+                                   int64_t *ray_index, float *rays, float *near, float *far, float *target_rgbs,
+                                   double *ray_alpha, uint8_t *truth_u8, float *gt_vis, float *gt_alpha, void *stream);
+
 /* Per-frame metrics of the reference's eval.py:100-218 on the 8-bit images of unpack_to_image, N frames of H x W
  * (H, W >= 7) per call.  SSIM is skimage.metrics.structural_similarity(x / 255., y / 255., multichannel=True, full=True)
  * as skimage's source defines it for float64 input: 7x7 uniform filter with scipy's 'reflect' border, sample covariance

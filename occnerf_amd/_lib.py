@@ -136,6 +136,9 @@ SIGNATURES = {
     'occnerf_whole_frame_gather': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32] + [_vp] * 9 + [_vp]),
     'occnerf_view_frame_gather': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     'occnerf_undistort_u8': (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'occnerf_resize_frame': (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32] + [_vp] * 8 + [_vp] * 4 + [_vp, _vp, _vp, _vp]),
+    'occnerf_patch_batch_f64': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, C.c_double, _vp] + [_vp] * 12 + [_vp]),
+    'occnerf_whole_frame_gather_f64': (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32] + [_vp] * 9 + [_vp]),
     'occnerf_frame_metrics_workspace_bytes': (_i64, [_i32, _i32, _i32]),
     'occnerf_frame_metrics': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     'occnerf_progress_tile_blocks': (_i32, [_i32, _i32]),

@@ -91,14 +91,17 @@ _DEFAULTS = {
     'freeview': {'frame_idx': 0, 'src_type': 'zju_mocap'}, 'tpose': {}, 'movement': {},
     # train.dataset_path: a prepared dataset directory (occnerf_amd/dataset.py) -- train.py then trains on it and `movement` /
     # `progress` read it; None: the synthetic subject.  train.images_prescaled: with resize_img_scale != 1, the PNGs are
-    # already at the training size (only K is scaled; nothing is resized here).  train.prepare_frames: undistort the frames of
+    # already at the training size (only K is scaled; nothing is resized here).  train.resize_frames: with resize_img_scale
+    # != 1, resize every batch and frame to the training size as the reference does (the float64 blend with the Lanczos
+    # filter, the mask with the bilinear one; occnerf_amd/resize.py, csrc/resize.hip); False refuses such a scale unless
+    # the PNGs are prescaled.  train.prepare_frames: undistort the frames of
     # cameras with 'distortions' and apply crop_image_scale when the dataset is opened (occnerf_amd/dataset.py); False refuses both
     # train.seed: the loader's host RNG (frame order, patch draws, background colours); train.prefetch: build batch t+1 on a
     # side stream while step t runs
     # train.save_checkpt_interval / save_model_interval, save_all, progress.dump_interval: the reference's checkpoint and
     # progress-dump schedule (occnerf_amd/trainer.py; its default.yaml:93-94, :106, :145); progress.dump_interval 0: no dumps.
     # `resume True` continues from <load_net>.tar in the logdir (`latest` where load_net names the seeded checkpoint)
-    'train': {'dataset_path': None, 'images_prescaled': False, 'prepare_frames': True, 'seed': 0, 'prefetch': True,
+    'train': {'dataset_path': None, 'images_prescaled': False, 'resize_frames': False, 'prepare_frames': True, 'seed': 0, 'prefetch': True,
               'save_checkpt_interval': 2000, 'save_model_interval': 40000},
     'progress': {'dump_interval': 500}, 'save_all': True,
     # the simulated occlusion of the reference's training set (core/data/occnerf/train.py:286-287): the mask columns

@@ -26,14 +26,16 @@ struct PatchDraws {
 };
 
 // class 0: subject, class 1: box and not subject
-__device__ __forceinline__ bool in_class(const uint8_t *__restrict__ alpha, const uint8_t *__restrict__ box, int p, int cls) {
-    const bool subject = alpha[(size_t)p * 3] > 0;
+template <class Pixels>
+__device__ __forceinline__ bool in_class(const Pixels &px, const uint8_t *__restrict__ box, int p, int cls) {
+    const bool subject = px.subject((size_t)p);
     return cls == 0 ? subject : (box[p] != 0 && !subject);
 }
 
-__global__ __launch_bounds__(kBatchThreads) void batch_classify_kernel(const uint8_t *__restrict__ alpha,
-                                                                      const uint8_t *__restrict__ box, int H, int W,
-                                                                      int32_t *__restrict__ row_counts) {
+// Pixels: where the frame's pixels are read from, PixelsU8 or PixelsF64 (batch_common.h)
+template <class Pixels>
+__global__ __launch_bounds__(kBatchThreads) void batch_classify_kernel(const Pixels px, const uint8_t *__restrict__ box,
+                                                                      int H, int W, int32_t *__restrict__ row_counts) {
     __shared__ int red[kBatchWaves];
     const int row = blockIdx.x;
     int n0 = 0, n1 = 0;
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_classify_kernel(const uin
         bool s = false, o = false;
         if (x < W) {
             const int p = row * W + x;
-            s = alpha[(size_t)p * 3] > 0;
+            s = px.subject((size_t)p);
             o = box[p] != 0 && !s;
         }
         n0 += __popcll(__ballot(s));                   // wave-uniform
@@ -57,8 +59,9 @@ __global__ __launch_bounds__(kBatchThreads) void batch_classify_kernel(const uin
     }
 }
 
-__global__ __launch_bounds__(kBatchThreads) void batch_pick_kernel(const uint8_t *__restrict__ alpha,
-                                                                  const uint8_t *__restrict__ box, int H, int W, int size,
+template <class Pixels>
+__global__ __launch_bounds__(kBatchThreads) void batch_pick_kernel(const Pixels px, const uint8_t *__restrict__ box, int H,
+                                                                  int W, int size,
                                                                   PatchDraws draws, double subject_ratio,
                                                                   const int32_t *__restrict__ row_counts,
                                                                   int32_t *__restrict__ xy_min) {
@@ -101,13 +104,13 @@ __global__ __launch_bounds__(kBatchThreads) void batch_pick_kernel(const uint8_t
         const int perw = (W + kBatchThreads - 1) / kBatchThreads;
         const int x0 = min(t * perw, W), x1 = min(x0 + perw, W);
         int sw = 0;
-        for (int x = x0; x < x1; x++) sw += in_class(alpha, box, cy * W + x, cls) ? 1 : 0;
+        for (int x = x0; x < x1; x++) sw += in_class(px, box, cy * W + x, cls) ? 1 : 0;
         int totalw;
         const int ew = block_excl_scan(sw, red, totalw);
         if (rem_row >= ew && rem_row < ew + sw) {
             int rem = rem_row - ew;
             for (int x = x0; x < x1; x++) {
-                if (in_class(alpha, box, cy * W + x, cls)) {
+                if (in_class(px, box, cy * W + x, cls)) {
                     if (rem == 0) {
                         found[0] = x;
                         break;
@@ -132,9 +135,8 @@ struct BatchOut {
     int32_t *patch_div_indices, *pix_of_row, *row_of_pix, *n_rows;
 };
 
-__global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8_t *__restrict__ image,
-                                                                    const uint8_t *__restrict__ alpha,
-                                                                    const float *__restrict__ rays8,
+template <class Pixels>
+__global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const Pixels px, const float *__restrict__ rays8,
                                                                     const uint8_t *__restrict__ box, int W, int n_patches,
                                                                     int size, double bg0, double bg1, double bg2,
                                                                     const int32_t *__restrict__ xy_min, BatchOut out) {
@@ -165,7 +167,7 @@ __global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8
         float rgb[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {                  // train.py:296-297, :398 in float64, one rounding per operator
-            rgb[c] = blend_target(alpha[(size_t)p * 3 + c], image[(size_t)p * 3 + c], bg[c]);
+            rgb[c] = px.target((size_t)p, c, bg[c]);
             out.target_patches[pix * 3 + c] = rgb[c];
         }
         out.patch_masks[pix] = hit ? 1 : 0;
@@ -183,18 +185,15 @@ __global__ __launch_bounds__(kBatchThreads) void batch_gather_kernel(const uint8
     }
 }
 
-}  // namespace occ
-
-OCC_API int32_t occnerf_patch_batch_max_patches(void) { return occ::kMaxPatches; }
-
-OCC_API int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
-                                int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u,
-                                double subject_ratio, const float *h_bgcolor, int32_t *row_counts, float *rays, float *near,
-                                float *far, float *target_rgbs, float *target_patches, uint8_t *patch_masks,
-                                int32_t *patch_div_indices, int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix,
-                                int32_t *n_rows, void *stream) {
-    using namespace occ;
-    OCC_REQUIRE(image && alpha && rays8 && box_mask && h_u && h_bgcolor && row_counts && rays && near && far && target_rgbs &&
+// The three launches from either pixel source; `first` and `second` are its two pointers, checked with the rest.
+template <class Pixels>
+static int patch_batch_from(const Pixels px, const void *first, const void *second, const float *rays8,
+                            const uint8_t *box_mask, int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u,
+                            double subject_ratio, const float *h_bgcolor, int32_t *row_counts, float *rays, float *near,
+                            float *far, float *target_rgbs, float *target_patches, uint8_t *patch_masks,
+                            int32_t *patch_div_indices, int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix,
+                            int32_t *n_rows, void *stream) {
+    OCC_REQUIRE(first && second && rays8 && box_mask && h_u && h_bgcolor && row_counts && rays && near && far && target_rgbs &&
                     target_patches && patch_masks && patch_div_indices && xy_min && pix_of_row && row_of_pix && n_rows,
                 "patch_batch: null argument");
     OCC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < (1ll << 28), "patch_batch: bad image size %d x %d", H, W);
@@ -209,12 +208,38 @@ OCC_API int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, cons
     }
     for (int p = n_patches; p < kMaxPatches; p++) draws.u[p][0] = draws.u[p][1] = 0.0;
     hipStream_t st = as_stream(stream);
-    hipLaunchKernelGGL(batch_classify_kernel, dim3(H), dim3(kBatchThreads), 0, st, alpha, box_mask, H, W, row_counts);
-    hipLaunchKernelGGL(batch_pick_kernel, dim3(n_patches), dim3(kBatchThreads), 0, st, alpha, box_mask, H, W, size, draws,
+    hipLaunchKernelGGL(batch_classify_kernel<Pixels>, dim3(H), dim3(kBatchThreads), 0, st, px, box_mask, H, W, row_counts);
+    hipLaunchKernelGGL(batch_pick_kernel<Pixels>, dim3(n_patches), dim3(kBatchThreads), 0, st, px, box_mask, H, W, size, draws,
                        subject_ratio, (const int32_t *)row_counts, xy_min);
     BatchOut out{rays, near, far, target_rgbs, target_patches, patch_masks, patch_div_indices, pix_of_row, row_of_pix, n_rows};
-    hipLaunchKernelGGL(batch_gather_kernel, dim3(n_patches), dim3(kBatchThreads), 0, st, image, alpha, rays8, box_mask, W,
+    hipLaunchKernelGGL(batch_gather_kernel<Pixels>, dim3(n_patches), dim3(kBatchThreads), 0, st, px, rays8, box_mask, W,
                        n_patches, size, (double)h_bgcolor[0], (double)h_bgcolor[1], (double)h_bgcolor[2],
                        (const int32_t *)xy_min, out);
     return check_launch("patch_batch");
+}
+
+}  // namespace occ
+
+OCC_API int32_t occnerf_patch_batch_max_patches(void) { return occ::kMaxPatches; }
+
+OCC_API int occnerf_patch_batch(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
+                                int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u,
+                                double subject_ratio, const float *h_bgcolor, int32_t *row_counts, float *rays, float *near,
+                                float *far, float *target_rgbs, float *target_patches, uint8_t *patch_masks,
+                                int32_t *patch_div_indices, int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix,
+                                int32_t *n_rows, void *stream) {
+    return occ::patch_batch_from(occ::PixelsU8{image, alpha}, image, alpha, rays8, box_mask, H, W, n_patches, size, h_u,
+                                 subject_ratio, h_bgcolor, row_counts, rays, near, far, target_rgbs, target_patches,
+                                 patch_masks, patch_div_indices, xy_min, pix_of_row, row_of_pix, n_rows, stream);
+}
+
+OCC_API int occnerf_patch_batch_f64(const double *img64, const double *alpha64, const float *rays8, const uint8_t *box_mask,
+                                    int32_t H, int32_t W, int32_t n_patches, int32_t size, const double *h_u,
+                                    double subject_ratio, const float *h_bgcolor, int32_t *row_counts, float *rays,
+                                    float *near, float *far, float *target_rgbs, float *target_patches, uint8_t *patch_masks,
+                                    int32_t *patch_div_indices, int32_t *xy_min, int32_t *pix_of_row, int32_t *row_of_pix,
+                                    int32_t *n_rows, void *stream) {
+    return occ::patch_batch_from(occ::PixelsF64{img64, alpha64}, img64, alpha64, rays8, box_mask, H, W, n_patches, size, h_u,
+                                 subject_ratio, h_bgcolor, row_counts, rays, near, far, target_rgbs, target_patches,
+                                 patch_masks, patch_div_indices, xy_min, pix_of_row, row_of_pix, n_rows, stream);
 }

@@ -90,6 +90,33 @@ __device__ __forceinline__ float blend_target(uint8_t m, uint8_t image, double b
     return (float)__ddiv_rn(__dadd_rn(fg, bk), 255.0);
 }
 
+// Where batch.hip and frame.hip read a frame's pixels from: the template parameter of their kernels.  p is the flat pixel
+// index, c the channel.
+//   subject(p)       the pixel belongs to the subject (train.py:470: alpha channel 0 > 0)
+//   target(p, c, bg) the training target, float32 in 0..1 (:398)
+//   alpha(p, c)      ray_alpha, float64
+//   alpha0(p)        gt_alpha: float32 of the mask's channel 0
+// PixelsU8: the resident uint8 photograph and mask, blended per pixel.
+struct PixelsU8 {
+    const uint8_t *__restrict__ image, *__restrict__ mask;
+    __device__ __forceinline__ bool subject(size_t p) const { return mask[p * 3] > 0; }
+    __device__ __forceinline__ float target(size_t p, int c, double bg) const {
+        return blend_target(mask[p * 3 + c], image[p * 3 + c], bg);
+    }
+    __device__ __forceinline__ double alpha(size_t p, int c) const { return __ddiv_rn((double)mask[p * 3 + c], 255.0); }
+    __device__ __forceinline__ float alpha0(size_t p) const { return (float)__ddiv_rn((double)mask[p * 3], 255.0); }
+};
+
+// PixelsF64: a frame occnerf_resize_frame has resized: img64 is the blend before its division by
+// 255, already over the background, and alpha64 the resized mask / 255.
+struct PixelsF64 {
+    const double *__restrict__ img64, *__restrict__ alpha64;
+    __device__ __forceinline__ bool subject(size_t p) const { return alpha64[p * 3] > 0.0; }
+    __device__ __forceinline__ float target(size_t p, int c, double) const { return (float)__ddiv_rn(img64[p * 3 + c], 255.0); }
+    __device__ __forceinline__ double alpha(size_t p, int c) const { return alpha64[p * 3 + c]; }
+    __device__ __forceinline__ float alpha0(size_t p) const { return (float)alpha64[p * 3]; }
+};
+
 // image_util.py:19-20 to_8b_image: (255. * clip(x, 0, 1)).astype(uint8) in float32, truncation.
 __device__ __forceinline__ uint8_t to_8b(float x) {
     x = x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x);          // np.clip (NaN propagates in numpy; not produced by the renderer)

@@ -53,9 +53,9 @@ struct FrameOut {
     float *gt_vis, *gt_alpha;
 };
 
-__global__ __launch_bounds__(kBatchThreads) void frame_gather_kernel(const uint8_t *__restrict__ image,
-                                                                    const uint8_t *__restrict__ alpha,
-                                                                    const float *__restrict__ rays8,
+// Pixels: where the frame's pixels are read from, PixelsU8 or PixelsF64 (batch_common.h)
+template <class Pixels>
+__global__ __launch_bounds__(kBatchThreads) void frame_gather_kernel(const Pixels px, const float *__restrict__ rays8,
                                                                     const uint8_t *__restrict__ box, int W, double bg0,
                                                                     double bg1, double bg2,
                                                                     const int32_t *__restrict__ row_start, int R,
@@ -73,15 +73,14 @@ __global__ __launch_bounds__(kBatchThreads) void frame_gather_kernel(const uint8
         const int row = base + chunk_rank(hit, red, chunk);
         base += chunk;
         if (!live) continue;
-        const uint8_t m[3] = {alpha[p * 3], alpha[p * 3 + 1], alpha[p * 3 + 2]};
-        const float a0 = (float)__ddiv_rn((double)m[0], 255.0);
+        const float a0 = px.alpha0(p);
         out.gt_alpha[p] = a0;
         out.gt_vis[p] = hit ? a0 : 0.0f;
         float rgb[3];
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             // inside the box the truth image shows the blended photograph, outside float32(bgcolor / 255) (unpack_to_image)
-            rgb[c] = hit ? blend_target(m[c], image[p * 3 + c], bg[c]) : (float)__ddiv_rn(bg[c], 255.0);
+            rgb[c] = hit ? px.target(p, c, bg[c]) : (float)__ddiv_rn(bg[c], 255.0);
             out.truth_u8[p * 3 + c] = to_8b(rgb[c]);
         }
         if (hit && row < R) {                          // row < R: a caller's R below the scan's total cannot write past the end
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(kBatchThreads) void frame_gather_kernel(const uint8
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 out.target_rgbs[(int64_t)row * 3 + c] = rgb[c];
-                out.ray_alpha[(int64_t)row * 3 + c] = __ddiv_rn((double)m[c], 255.0);
+                out.ray_alpha[(int64_t)row * 3 + c] = px.alpha(p, c);
             }
         }
     }
@@ -108,19 +107,44 @@ OCC_API int occnerf_whole_frame_count(const uint8_t *box_mask, int32_t H, int32_
     return check_launch("whole_frame_count");
 }
 
-OCC_API int occnerf_whole_frame_gather(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
-                                       int32_t H, int32_t W, const float *h_bgcolor, const int32_t *row_start, int32_t R,
-                                       int64_t *ray_index, float *rays, float *near, float *far, float *target_rgbs,
-                                       double *ray_alpha, uint8_t *truth_u8, float *gt_vis, float *gt_alpha, void *stream) {
-    using namespace occ;
-    OCC_REQUIRE(image && alpha && rays8 && box_mask && h_bgcolor && row_start && truth_u8 && gt_vis && gt_alpha,
+namespace occ {
+
+// The gather from either pixel source; `first` and `second` are its two pointers, checked with the rest.
+template <class Pixels>
+static int whole_frame_gather_from(const Pixels px, const void *first, const void *second, const float *rays8,
+                                   const uint8_t *box_mask, int32_t H, int32_t W, const float *h_bgcolor,
+                                   const int32_t *row_start, int32_t R, int64_t *ray_index, float *rays, float *near,
+                                   float *far, float *target_rgbs, double *ray_alpha, uint8_t *truth_u8, float *gt_vis,
+                                   float *gt_alpha, void *stream) {
+    OCC_REQUIRE(first && second && rays8 && box_mask && h_bgcolor && row_start && truth_u8 && gt_vis && gt_alpha,
                 "whole_frame_gather: null argument");
     OCC_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < (1ll << 28), "whole_frame_gather: bad image size %d x %d", H, W);
     OCC_REQUIRE(R >= 0 && (int64_t)R <= (int64_t)H * W, "whole_frame_gather: R=%d outside [0, %lld]", R, (long long)H * W);
     OCC_REQUIRE(R == 0 || (ray_index && rays && near && far && target_rgbs && ray_alpha),
                 "whole_frame_gather: null ray output with R=%d", R);
     FrameOut out{ray_index, rays, near, far, target_rgbs, ray_alpha, truth_u8, gt_vis, gt_alpha};
-    hipLaunchKernelGGL(frame_gather_kernel, dim3(H), dim3(kBatchThreads), 0, as_stream(stream), image, alpha, rays8, box_mask,
+    hipLaunchKernelGGL(frame_gather_kernel<Pixels>, dim3(H), dim3(kBatchThreads), 0, as_stream(stream), px, rays8, box_mask,
                        W, (double)h_bgcolor[0], (double)h_bgcolor[1], (double)h_bgcolor[2], row_start, R, out);
     return check_launch("whole_frame_gather");
+}
+
+}  // namespace occ
+
+OCC_API int occnerf_whole_frame_gather(const uint8_t *image, const uint8_t *alpha, const float *rays8, const uint8_t *box_mask,
+                                       int32_t H, int32_t W, const float *h_bgcolor, const int32_t *row_start, int32_t R,
+                                       int64_t *ray_index, float *rays, float *near, float *far, float *target_rgbs,
+                                       double *ray_alpha, uint8_t *truth_u8, float *gt_vis, float *gt_alpha, void *stream) {
+    return occ::whole_frame_gather_from(occ::PixelsU8{image, alpha}, image, alpha, rays8, box_mask, H, W, h_bgcolor, row_start,
+                                        R, ray_index, rays, near, far, target_rgbs, ray_alpha, truth_u8, gt_vis, gt_alpha,
+                                        stream);
+}
+
+OCC_API int occnerf_whole_frame_gather_f64(const double *img64, const double *alpha64, const float *rays8,
+                                           const uint8_t *box_mask, int32_t H, int32_t W, const float *h_bgcolor,
+                                           const int32_t *row_start, int32_t R, int64_t *ray_index, float *rays, float *near,
+                                           float *far, float *target_rgbs, double *ray_alpha, uint8_t *truth_u8,
+                                           float *gt_vis, float *gt_alpha, void *stream) {
+    return occ::whole_frame_gather_from(occ::PixelsF64{img64, alpha64}, img64, alpha64, rays8, box_mask, H, W, h_bgcolor,
+                                        row_start, R, ray_index, rays, near, far, target_rgbs, ray_alpha, truth_u8, gt_vis,
+                                        gt_alpha, stream);
 }

@@ -18,12 +18,16 @@ a dataset is refused by name.
 
 What is NOT the reference's, each refused by name where it would matter:
   * upsample_pc (:384-385, needs trimesh and the SMPL faces);
-  * resize_img_scale != 1 on PNGs that are not already at the training size.  The reference blends at full size and then
-    resizes the float image with cv2's Lanczos filter and the mask with its bilinear one (:306-314); neither filter nor that
-    order exists here, so nothing is resized: with `train.images_prescaled True` the PNGs are taken to BE the training images
-    (resized by the user, any filter) and only K[:2] is scaled (:430); otherwise the scale is refused.  Prescaled PNGs no
-    longer match the stored K, so 'distortions' or a crop together with a scale other than 1 are refused too.  Resizing
-    needs float-resident frames and is the next step;
+  * resize_img_scale != 1 unless `resize_frames` (train.resize_frames True) or `images_prescaled` is set.  The reference
+    blends at full size and then resizes the float image with cv2's Lanczos filter and the mask with its bilinear one
+    (:306-314).  With resize_frames that is done here (resize.py on the host, csrc/resize.hip through ops.resize_frame on
+    the device): the prepared full-size uint8 pair stays resident (`src_height` x `src_width`),
+    `height` x `width` is the training size rint(H s) x rint(W s) of every ray buffer, and each batch or frame is resized
+    with its own background colour into a float64 frame of the loader's buffer set, which the _f64 entries of the batch
+    and frame builders read.  'distortions' and a crop are then legal with a scale: the full-size PNG still matches K.
+    With `train.images_prescaled True` instead, the PNGs are taken to BE the training images (resized by the user, any
+    filter) and only K[:2] is scaled (:430); prescaled PNGs no longer match the stored K, so 'distortions' or a crop
+    together with a scale other than 1 are refused there.  With neither key the scale is refused;
   * 12 or 14 distortion coefficients (OpenCV's thin prism and tilt models) and a skewed camera matrix;
   * the 'verts' key (:381, :416): it needs an SMPL model and Network.forward does not read it.
 """
@@ -35,6 +39,7 @@ import torch
 
 from . import synth
 from .undistort import undistort_u8
+from . import resize
 from .ahead import FrameAhead, cuda_device
 
 WHOLE_FRAME_KEYS = ('rays', 'near', 'far', 'ray_mask', 'bgcolor', 'target_rgbs', 'ray_alpha')
@@ -161,16 +166,21 @@ class CameraRaysAhead:
     an H x W camera and its box test (ops.gen_rays), the hits above every image row (ops.whole_frame_count) and, on the
     host, their total R.  A buffer set is rays8 [H*W,8], box [H*W] and row_start [H+1]."""
 
-    def __init__(self, device, H, W, prefetch):
+    def __init__(self, device, H, W, prefetch, extra=None):
+        """extra: a callable -> further tensors of every buffer set (a resized float frame), for start's `also`."""
         from . import ops
         self._ops, self.H, self.W = ops, H, W
-        self._ahead = FrameAhead(device, lambda: {
+        self._ahead = FrameAhead(device, lambda: dict({
             'rays8': torch.empty(H * W, 8, device=device, dtype=torch.float32),
             'box': torch.empty(H * W, device=device, dtype=torch.uint8),
-            'row_start': torch.empty(H + 1, device=device, dtype=torch.int32)}, host_words=1, prefetch=prefetch)
+            'row_start': torch.empty(H + 1, device=device, dtype=torch.int32)}, **(extra() if extra else {})),
+            host_words=1, prefetch=prefetch)
 
-    def start(self, item, K, E, box_min, box_max):
+    def start(self, item, K, E, box_min, box_max, also=None):
+        """also(bufs): more work for the same buffer set, enqueued ahead with the rays."""
         def enqueue(bufs, _item):
+            if also is not None:
+                also(bufs)
             self._ops.gen_rays(K, E, self.H, self.W, box_min, box_max, self._ahead.device, out=(bufs['rays8'], bufs['box']))
             self._ops.whole_frame_count(bufs['box'], self.H, self.W, bufs['row_start'])
             return bufs['row_start'][self.H:]
@@ -209,11 +219,18 @@ class PreparedDataset(Subject):
     `self.images` / `self.alphas` (whole_frame(), views.py) hold prepared frames on either route, identical ones.
     prepare_device: the GPU that prepares the frames of a dataset that itself stays on the host (device=None).
 
+    resize_frames=True with a resize_img_scale other than 1 resizes every batch and frame to the training size `height` x
+    `width` = rint(src_height s) x rint(src_width s) (the module docstring): `self.images` /
+    `self.alphas` stay the prepared full-size pair, `empty` is the reference's test on the resized mask (its float64 sum
+    below 1), and the tap tables are built once (`self.resize_tables`) and uploaded with the frames.  At scale 1 the key
+    changes nothing; together with images_prescaled it is a ValueError.
+
     device=None keeps everything on the host (the host constants can be checked without a GPU)."""
 
     def __init__(self, dataset_path, device='cuda:0', skip=1, maxframes=-1, bbox_offset=0.3, volume_size=32,
                  resize_img_scale=1.0, images_prescaled=False, occlude=False, occlusion=None,
-                 crop_image_scale=(-1, -1), upsample_pc=False, prepare_frames=False, prepare_device=None):
+                 crop_image_scale=(-1, -1), upsample_pc=False, prepare_frames=False, prepare_device=None,
+                 resize_frames=False):
         from PIL import Image
         if not os.path.isdir(os.path.join(dataset_path, 'images')):
             raise FileNotFoundError(f'{dataset_path}: no images/ directory: not a prepared dataset')
@@ -225,12 +242,16 @@ class PreparedDataset(Subject):
             raise NotImplementedError('upsample_pc: subdividing the SMPL mesh (train.py:384-385) needs trimesh and the SMPL '
                                       'faces; not built')
         scale = self.resize_img_scale = float(resize_img_scale)
-        if scale != 1.0 and not images_prescaled:
+        if resize_frames and images_prescaled:
+            raise ValueError('resize_frames together with images_prescaled: the PNGs are either resized here '
+                             '(train.resize_frames) or already at the training size (train.images_prescaled), not both')
+        resizing = self.resizing = bool(resize_frames) and scale != 1.0      # scale 1: nothing is resized (train.py:306)
+        if scale != 1.0 and not images_prescaled and not resizing:
             raise NotImplementedError(
-                f'resize_img_scale={scale}: the reference resizes the blended image with cv2 (train.py:306-314), which is not '
-                'available. Resize the PNGs yourself and set train.images_prescaled True (K is then scaled, the PNGs are '
-                'not), or set resize_img_scale 1')
-        if scale != 1.0 and crop is not None:
+                f'resize_img_scale={scale}: frames are resized (train.py:306-314) only when asked to. Set train.resize_frames '
+                'True (the blend is resized with the Lanczos filter, the mask with the bilinear one), or resize the PNGs '
+                'yourself and set train.images_prescaled True (K is then scaled, the PNGs are not), or set resize_img_scale 1')
+        if scale != 1.0 and crop is not None and not resizing:
             raise NotImplementedError(f'crop_image_scale={list(crop)} with resize_img_scale={scale}: the crop (train.py:300-304) '
                                       'is in pixels of the full-size image, which prescaled PNGs no longer are')
         if prepare_device is None:
@@ -254,7 +275,7 @@ class PreparedDataset(Subject):
         if not names:
             raise FileNotFoundError(f'{dataset_path}/images holds no PNG')
         self.framelist, self.occlude = names, bool(occlude)
-        self.frames, self.images, self.alphas, raw_size = [], [], [], None
+        self.frames, self.images, self.alphas, raw_size, self.resize_tables = [], [], [], None, None
         for idx, name in enumerate(names):
             if name not in cameras:
                 raise KeyError(f'{dataset_path}/cameras.pkl has no camera for frame {name}')
@@ -262,7 +283,7 @@ class PreparedDataset(Subject):
             if distorted and not prepare_frames:
                 raise NotImplementedError(f"frame {name}: the camera has 'distortions'; undistorting the image "
                                           '(train.py:290-294, cv2.undistort) is not built. Undistort the PNGs and drop the key')
-            if distorted and scale != 1.0:
+            if distorted and scale != 1.0 and not resizing:
                 raise NotImplementedError(f"frame {name}: the camera has 'distortions' and resize_img_scale is {scale}: "
                                           'prescaled PNGs no longer match the stored intrinsics, so they cannot be undistorted')
             img = np.array(Image.open(os.path.join(dataset_path, 'images', name + '.png')).convert('RGB'))
@@ -283,7 +304,14 @@ class PreparedDataset(Subject):
             elif window is not None:
                 y0, x0, h, w = window
                 img, alpha = img[y0:y0 + h, x0:x0 + w], alpha[y0:y0 + h, x0:x0 + w]
-            self.height, self.width = int(img.shape[0]), int(img.shape[1])
+            self.src_height, self.src_width = int(img.shape[0]), int(img.shape[1])
+            self.height, self.width = self.src_height, self.src_width
+            empty = int(alpha.astype(np.int64).sum()) < 255
+            if resizing:                             # the training size; `empty` is the reference's test on the resized mask
+                if self.resize_tables is None:
+                    self.resize_tables = resize.frame_tables(self.src_height, self.src_width, scale)
+                self.height, self.width = self.resize_tables['size']
+                empty = bool(np.sum(resize.resize_blend(None, alpha, None, scale, self.resize_tables)[1]) < 1)
             info = mesh_infos[name]
             poses = info['poses'].astype('float32')
             joints = info['joints'].astype('float32')
@@ -302,7 +330,7 @@ class PreparedDataset(Subject):
                 'dst_bbox_min': bbox['min_xyz'], 'dst_bbox_max': bbox['max_xyz'], 'joints': joints, 'poses': poses,
                 'betas': info['betas'].astype('float32'), 'Rh': synth.rodrigues_exact(Rh).astype(np.float32), 'Th': Th,
                 'dst_Rs': dst_Rs, 'dst_Ts': dst_Ts, 'dst_posevec': poses[3:] + 1e-2,
-                'empty': int(alpha.astype(np.int64).sum()) < 255,
+                'empty': empty,
                 # what the derived cameras of views.py start from: the camera as calibrated and the body's axis-angle Rh
                 'extrinsics': np.asarray(cameras[name]['extrinsics']), 'Rh_vec': Rh})
             self.images.append(np.ascontiguousarray(img))
@@ -327,7 +355,9 @@ class PreparedDataset(Subject):
 
     def upload(self, dev):
         """The images, the masks (uint8 [H,W,3] each) and the per-frame constants, with the subject's."""
+        from . import ops
         return dict(Subject.upload(self, dev),
+                    resize=ops.upload_resize_tables(self.resize_tables, dev) if self.resizing else None,
                     image=[torch.from_numpy(a).to(dev) for a in self.images],
                     alpha=[torch.from_numpy(a).to(dev) for a in self.alphas],
                     frame=[self.upload_pose(f, dev) for f in self.frames])
@@ -346,7 +376,7 @@ class PreparedDataset(Subject):
                    images_prescaled=bool(tr.get('images_prescaled', False)), occlude=cfg.get('occlude', False) is True,
                    occlusion=cfg.get('occlusion'), crop_image_scale=crop,
                    upsample_pc=bool(cfg.get('upsample_pc', False)), prepare_frames=bool(tr.get('prepare_frames', True)),
-                   prepare_device=prepare_device)
+                   prepare_device=prepare_device, resize_frames=bool(tr.get('resize_frames', False)))
 
     def __len__(self):
         return len(self.framelist)
@@ -359,13 +389,51 @@ class PreparedDataset(Subject):
         """The same on the device (uploaded by to_device)."""
         return self.constants(self._dev['frame'][i], device=True)
 
+    def resized_frame(self, i, bgcolor):
+        """(img64, alpha64) of frame i at the training size, numpy on the host (resize.resize_blend): the blend over
+        `bgcolor`, not divided by 255, and the mask / 255."""
+        if not self.resizing:
+            raise RuntimeError('resized_frame: the dataset was opened without resize_frames (or at scale 1)')
+        return resize.resize_blend(self.images[i], self.alphas[i], bgcolor, self.resize_img_scale, self.resize_tables)
+
+    def truth_u8(self, i):
+        """The photograph of frame i as the truth panel of views.py shows it, uint8 [height, width, 3]: the resident image,
+        or with resize_frames the Lanczos resize of the photograph itself (the blend under a full mask is the photograph,
+        exactly) through to_8b_image: uint8(255.f * clip(float32(img64 / 255.), 0, 1))."""
+        if not self.resizing:
+            return self.images[i]
+        full = np.full_like(self.images[i], 255)
+        img64 = resize.resize_blend(self.images[i], full, [0., 0., 0.], self.resize_img_scale, self.resize_tables)[0]
+        return (np.float32(255.) * np.clip((img64 / 255.).astype('float32'), 0., 1.)).astype(np.uint8)
+
+    def truth_u8_device(self, i):
+        """truth_u8 on the device the dataset was uploaded to (ops.resize_frame, then the panel's few elementwise steps), on
+        the current stream; identical to the host's."""
+        if not self.resizing:
+            return self._dev['image'][i]
+        from . import ops
+        if self._dev.get('full_mask') is None:
+            self._dev['full_mask'] = torch.full_like(self._dev['image'][i], 255)
+        img64 = ops.resize_frame(self._dev['image'][i], self._dev['full_mask'], self._dev['resize'], [0., 0., 0.])[0]
+        return (img64 / 255.).float().clamp_(0., 1.).mul_(255.).to(torch.uint8)
+
+    def gt_alpha(self, i):
+        """float32 [height, width]: channel 0 of frame i's mask at the training size, as the metrics take it."""
+        if self.resizing:
+            return resize.resize_blend(None, self.alphas[i], None, self.resize_img_scale, self.resize_tables)[1][:, :, 0] \
+                .astype('float32')
+        return (self.alphas[i][:, :, 0] / 255.).astype('float32')
+
     def whole_frame(self, i, bgcolor):
         """Frame i as the reference's `ray_shoot_mode 'image'` dict (train.py:353-537 without the patch keys), numpy on the
         host: every ray that hits the box, with `target_rgbs` and `ray_alpha`."""
         f, H, W = self.frames[i], self.height, self.width
         bg = np.array(bgcolor, dtype='float32')
-        alpha = self.alphas[i] / 255.
-        img = alpha * self.images[i] + (1.0 - alpha) * bg[None, None, :]
+        if self.resizing:
+            img, alpha = self.resized_frame(i, bg)
+        else:
+            alpha = self.alphas[i] / 255.
+            img = alpha * self.images[i] + (1.0 - alpha) * bg[None, None, :]
         img = (img / 255.).astype('float32')
         out = host_frame(f['frame_name'], H, W, f['K'], f['E'], f['dst_bbox_min'], f['dst_bbox_max'], bg)
         out.update(target_rgbs=img.reshape(-1, 3)[out['ray_mask']], ray_alpha=alpha.reshape(-1, 3)[out['ray_mask']])
@@ -402,17 +470,28 @@ class WholeFrames:
         ds = self.dataset.to_device(device)
         H, W, n = ds.height, ds.width, len(ds)
         bg = np.array(self.bgcolor, dtype='float32')
-        ahead = CameraRaysAhead(ds.device, H, W, prefetch)
+        extra = None
+        if ds.resizing:                                        # the float frame of every buffer set, resized ahead
+            extra = lambda: dict(zip(('img64', 'alpha64'), ops.alloc_resize_frame(H, W, ds.device)))      # noqa: E731
+        ahead = CameraRaysAhead(ds.device, H, W, prefetch, extra)
 
         def start(i):
-            f = ds.frames[i]
-            return ahead.start(f, f['K'], f['E'], f['dst_bbox_min'], f['dst_bbox_max'])
+            f, also = ds.frames[i], None
+            if ds.resizing:
+                def also(bufs):
+                    ops.resize_frame(ds._dev['image'][i], ds._dev['alpha'][i], ds._dev['resize'], bg,
+                                     out=(bufs['img64'], bufs['alpha64']))
+            return ahead.start(f, f['K'], f['E'], f['dst_bbox_min'], f['dst_bbox_max'], also)
 
         pending = start(0) if n else None
         for i in range(n):
             bufs, R, f = ahead.take(pending)
-            out = ops.whole_frame(ds._dev['image'][i], ds._dev['alpha'][i], bufs['rays8'], bufs['box'], bg,
-                                  row_start=bufs['row_start'], R=R)
+            if ds.resizing:
+                out = ops.whole_frame_f64(bufs['img64'], bufs['alpha64'], bufs['rays8'], bufs['box'], bg,
+                                          row_start=bufs['row_start'], R=R)
+            else:
+                out = ops.whole_frame(ds._dev['image'][i], ds._dev['alpha'][i], bufs['rays8'], bufs['box'], bg,
+                                      row_start=bufs['row_start'], R=R)
             body = bufs['box'].view(H, W).clone()              # the buffer set is rewritten two frames on
             pending = start(i + 1) if i + 1 < n else None      # after the gather is enqueued, before the consumer renders
             data = {'rays': out['rays'], 'near': out['near'], 'far': out['far'], 'bgcolor': torch.from_numpy(bg),
@@ -512,8 +591,14 @@ class PatchBatchLoader:
         ds, f = self.dataset, self.dataset.frames[draw[0]]
         self._ops.gen_rays(f['K'], f['E'], ds.height, ds.width, f['dst_bbox_min'], f['dst_bbox_max'], ds.device,
                            out=(bufs['rays8'], bufs['box']))
-        out = self._ops.patch_batch(ds._dev['image'][frame], ds._dev['alpha'][frame], bufs['rays8'], bufs['box'],
-                                    self.n_patches, self.size, u, self.ratio, bg, out=bufs['out'])
+        if ds.resizing:                                # the batch's own background colour: resized per batch (section 7g)
+            self._ops.resize_frame(ds._dev['image'][frame], ds._dev['alpha'][frame], ds._dev['resize'], bg,
+                                   out=(bufs['img64'], bufs['alpha64']))
+            out = self._ops.patch_batch_f64(bufs['img64'], bufs['alpha64'], bufs['rays8'], bufs['box'],
+                                            self.n_patches, self.size, u, self.ratio, bg, out=bufs['out'])
+        else:
+            out = self._ops.patch_batch(ds._dev['image'][frame], ds._dev['alpha'][frame], bufs['rays8'], bufs['box'],
+                                        self.n_patches, self.size, u, self.ratio, bg, out=bufs['out'])
         return out['patch_div_indices'], out['n_rows']
 
     def _start(self):
@@ -523,11 +608,14 @@ class PatchBatchLoader:
                                'by HIP kernels, there is no CPU path')
         if self._ahead is None:                        # the buffers are allocated by the first next()
             dev, H, W = ds.device, ds.height, ds.width
-            self._ahead = FrameAhead(dev, lambda: {
-                'out': self._ops.alloc_patch_batch(self.n_patches, self.size, H, dev),
-                'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
-                'box': torch.empty(H * W, device=dev, dtype=torch.uint8)},
-                host_words=self.n_patches + 2, prefetch=self.prefetch)
+            def buffers():
+                bufs = {'out': self._ops.alloc_patch_batch(self.n_patches, self.size, H, dev),
+                        'rays8': torch.empty(H * W, 8, device=dev, dtype=torch.float32),
+                        'box': torch.empty(H * W, device=dev, dtype=torch.uint8)}
+                if ds.resizing:                        # the resized float frame: 48 bytes per training pixel
+                    bufs['img64'], bufs['alpha64'] = self._ops.alloc_resize_frame(H, W, dev)
+                return bufs
+            self._ahead = FrameAhead(dev, buffers, host_words=self.n_patches + 2, prefetch=self.prefetch)
         return self._ahead.start(self._draw(), self._enqueue)
 
     def __next__(self):

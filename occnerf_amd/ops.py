@@ -1006,6 +1006,20 @@ def patch_batch(image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio
     """The patch batch of one frame (include/occnerf_hip.h occnerf_patch_batch): image / alpha [H,W,3] uint8 on the device,
     rays8 / box_mask from gen_rays, u[n_patches,2] host uniforms in [0, 1), bgcolor[3] in 0..255 on the host.  -> the dict of
     alloc_patch_batch (filled in place when passed as `out`); the row count stays on the device in 'n_rows'."""
+    return _patch_batch('occnerf_patch_batch', torch.uint8, image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio,
+                        bgcolor, out)
+
+
+def patch_batch_f64(img64, alpha64, rays8, box_mask, n_patches, size, u, subject_ratio, bgcolor, out=None):
+    """patch_batch on a frame resize_frame has written (include/occnerf_hip.h occnerf_patch_batch_f64): img64 / alpha64
+    [H,W,3] float64 at the training size in the place of image / alpha; everything else as patch_batch."""
+    return _patch_batch('occnerf_patch_batch_f64', torch.float64, img64, alpha64, rays8, box_mask, n_patches, size, u,
+                        subject_ratio, bgcolor, out)
+
+
+def _patch_batch(entry, dtype, image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio, bgcolor, out):
+    if not torch.is_tensor(image) or not torch.is_tensor(alpha) or image.dim() != 3 or alpha.dim() != 3:
+        raise RuntimeError('patch_batch: image and alpha must be [H,W,3] tensors')
     H, W = int(image.shape[0]), int(image.shape[1])
     N, S = int(n_patches), int(size)
     if tuple(image.shape) != (H, W, 3) or tuple(alpha.shape) != (H, W, 3):
@@ -1032,8 +1046,8 @@ def patch_batch(image, alpha, rays8, box_mask, n_patches, size, u, subject_ratio
         if out[k].numel() != n:
             raise RuntimeError(f'patch_batch: out[{k!r}] holds {out[k].numel()} elements, the batch needs {n}')
     with _guard(image):
-        rc = _lib.lib().occnerf_patch_batch(
-            _chk(image, torch.uint8, 'image'), _chk(alpha, torch.uint8, 'alpha'), _chk(rays8, torch.float32, 'rays8'),
+        rc = getattr(_lib.lib(), entry)(
+            _chk(image, dtype, 'image'), _chk(alpha, dtype, 'alpha'), _chk(rays8, torch.float32, 'rays8'),
             _chk(box_mask, torch.uint8, 'box_mask'), H, W, N, S, u0.ctypes.data_as(C.c_void_p), float(subject_ratio), bgp,
             ptr['row_counts'], ptr['rays'], ptr['near'], ptr['far'], ptr['target_rgbs'], ptr['target_patches'],
             ptr['patch_masks'], ptr['patch_div_indices'], ptr['xy_min'], ptr['pix_of_row'], ptr['row_of_pix'], ptr['n_rows'],
@@ -1108,6 +1122,18 @@ def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, 
     row_start, R: the result of whole_frame_count and the host copy of row_start[H] (the loader reads it from pinned memory
     behind an event); both None: counted here and read back with one blocking copy.  out: a dict of alloc_whole_frame(H, W, R)
     to fill in place."""
+    return _whole_frame('occnerf_whole_frame_gather', torch.uint8, image, alpha, rays8, box_mask, bgcolor, row_start, R, out)
+
+
+def whole_frame_f64(img64, alpha64, rays8, box_mask, bgcolor, row_start=None, R=None, out=None):
+    """whole_frame on a frame resize_frame has written (include/occnerf_hip.h occnerf_whole_frame_gather_f64): img64 /
+    alpha64 [H,W,3] float64 at the training size in the place of image / alpha; bgcolor still colours truth_u8 outside the
+    box.  Everything else as whole_frame."""
+    return _whole_frame('occnerf_whole_frame_gather_f64', torch.float64, img64, alpha64, rays8, box_mask, bgcolor, row_start, R,
+                        out)
+
+
+def _whole_frame(entry, dtype, image, alpha, rays8, box_mask, bgcolor, row_start, R, out):
     if not torch.is_tensor(image) or not torch.is_tensor(alpha) or image.dim() != 3 or alpha.dim() != 3:
         raise RuntimeError('whole_frame: image and alpha must be [H,W,3] tensors')
     H, W = int(image.shape[0]), int(image.shape[1])
@@ -1115,7 +1141,7 @@ def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, 
         raise RuntimeError(f'whole_frame: image and alpha must both be [H,W,3], got {tuple(image.shape)}, {tuple(alpha.shape)}')
     if H * W >= 1 << 28:
         raise RuntimeError(f'whole_frame: H*W = {H} * {W} must be below 2^28')
-    pi, pa = _chk(image, torch.uint8, 'image'), _chk(alpha, torch.uint8, 'alpha')
+    pi, pa = _chk(image, dtype, 'image'), _chk(alpha, dtype, 'alpha')
     row_start, R, (pr, pb, ps) = _frame_rows('whole_frame', H, W, rays8, box_mask, row_start, R, image, alpha)
     if out is None:
         out = alloc_whole_frame(H, W, R, image.device)
@@ -1129,7 +1155,7 @@ def whole_frame(image, alpha, rays8, box_mask, bgcolor, row_start=None, R=None, 
             raise RuntimeError('whole_frame: `out` is on another device than the frame')
     bg, bgp = _host_f32(bgcolor, 3)
     with _guard(image):
-        rc = _lib.lib().occnerf_whole_frame_gather(
+        rc = getattr(_lib.lib(), entry)(
             pi, pa, pr, pb, H, W, bgp, ps, R, ptr['ray_index'], ptr['rays'], ptr['near'], ptr['far'], ptr['target_rgbs'],
             ptr['ray_alpha'], ptr['truth_u8'], ptr['gt_vis'], ptr['gt_alpha'], _stream(image))
     _lib.check(rc, 'whole_frame_gather')
@@ -1186,3 +1212,75 @@ def undistort_u8(image, mask, K, D, window=None, out=None):
         rc = _lib.lib().occnerf_undistort_u8(pi, pm, H, W, k.ctypes.data, d.ctypes.data, y0, x0, h, w, po, pom, _stream(image))
     _lib.check(rc, 'undistort_u8')
     return oi, om
+
+
+# ------------------------------------------------------------------ resizing a prepared frame to the training size
+_RESIZE_TABLES = ('x_lanczos', 'y_lanczos', 'x_bilinear', 'y_bilinear')
+
+
+def upload_resize_tables(tables, device):
+    """resize.frame_tables(H, W, s) -> what resize_frame takes: the four tables on `device` beside their host copies (the
+    entry checks the host offsets before it launches).  Built once per dataset."""
+    if torch.device(device).type != 'cuda':
+        raise RuntimeError(f'upload_resize_tables: {device} is not a GPU; resize.resize_blend is the host path')
+    out = {'size': tuple(int(v) for v in tables['size']), 'src_size': tuple(int(v) for v in tables['src_size']), 'device': {}}
+    for k in _RESIZE_TABLES:
+        off, wgt = tables[k]
+        off, wgt = np.ascontiguousarray(off, dtype=np.int32), np.ascontiguousarray(wgt, dtype=np.float32)
+        n, taps = out['size'][0 if k[0] == 'y' else 1], 8 if k.endswith('lanczos') else 2
+        if off.shape != (n, taps) or wgt.shape != (n, taps):
+            raise RuntimeError(f'upload_resize_tables: {k} must be [{n},{taps}], got offsets {off.shape}, weights {wgt.shape}')
+        out[k] = (off, wgt)
+        out['device'][k] = (torch.from_numpy(off).to(device), torch.from_numpy(wgt).to(device))
+    return out
+
+
+def alloc_resize_frame(h, w, device):
+    """(img64, alpha64): the float64 frame resize_frame fills, 48 bytes per training pixel."""
+    return (torch.empty(int(h), int(w), 3, device=device, dtype=torch.float64),
+            torch.empty(int(h), int(w), 3, device=device, dtype=torch.float64))
+
+
+def resize_frame(image, mask, tables, bgcolor=None, out=None):
+    """occnerf_amd.resize.resize_blend on the device (include/occnerf_hip.h occnerf_resize_frame): image [H,W,3] uint8 or
+    None (the mask alone) and mask [H,W,3] uint8 on one device, tables from upload_resize_tables for that device and size,
+    bgcolor[3] in 0..255 on the host -> (img64 or None, alpha64), float64 [h,w,3], on the current stream.  out: the pair to
+    fill in place (the first entry None without an image); it must not share memory with the inputs."""
+    if not torch.is_tensor(mask) or mask.dim() != 3 or mask.shape[2] != 3:
+        raise RuntimeError('resize_frame: mask must be a [H,W,3] tensor')
+    H, W = int(mask.shape[0]), int(mask.shape[1])
+    if H * W >= 1 << 28:
+        raise RuntimeError(f'resize_frame: H*W = {H} * {W} must be below 2^28')
+    pm, pi = _chk(mask, torch.uint8, 'mask'), _opt(image, torch.uint8, 'image')
+    if image is not None and (tuple(image.shape) != (H, W, 3) or image.device != mask.device):
+        raise RuntimeError(f'resize_frame: image must be [{H},{W},3] on the device of mask')
+    if not isinstance(tables, dict) or 'device' not in tables:
+        raise RuntimeError('resize_frame: tables must come from upload_resize_tables')
+    if tuple(tables['src_size']) != (H, W):
+        raise RuntimeError(f"resize_frame: the tables are those of a {tables['src_size'][1]} x {tables['src_size'][0]} frame, "
+                           f'the mask is {W} x {H}')
+    h, w = tables['size']
+    if image is not None and bgcolor is None:
+        raise RuntimeError('resize_frame: an image is blended over bgcolor, which is None')
+    if out is None:
+        pair = alloc_resize_frame(h, w, mask.device)
+        out = (None if image is None else pair[0], pair[1])
+    oi, oa = out
+    if (oi is None) != (image is None):
+        raise RuntimeError('resize_frame: out holds an image exactly when an image is given')
+    po, pa = _opt(oi, torch.float64, 'out image'), _chk(oa, torch.float64, 'out alpha')
+    if any(t is not None and (tuple(t.shape) != (h, w, 3) or t.device != mask.device) for t in (oi, oa)):
+        raise RuntimeError(f'resize_frame: out must be [{h},{w},3] on the device of mask')
+    dev, host = [], []
+    for k in _RESIZE_TABLES:
+        off, wgt = tables['device'][k]
+        if off.device != mask.device:
+            raise RuntimeError('resize_frame: the tables are on another device than the frame')
+        dev += [_chk(off, torch.int32, k + ' offsets'), _chk(wgt, torch.float32, k + ' weights')]
+        host.append(tables[k][0].ctypes.data_as(C.c_void_p))
+    bgp = None if image is None else _host_f32(bgcolor, 3)
+    with _guard(mask):
+        rc = _lib.lib().occnerf_resize_frame(pi, pm, H, W, h, w, *dev, *host, None if bgp is None else bgp[1], po, pa,
+                                             _stream(mask))
+    _lib.check(rc, 'resize_frame')
+    return oi, oa

@@ -23,7 +23,9 @@ PREPARED one: from_cfg opens the dataset with prepare_frames (dataset.py), so a 
 undistorted with that camera (freeview.py:156, backview.py:159); these loaders have no crop code, so nothing is cropped.
 An allview rig with 'distortions' undistorts the RAW photograph of the source frame with rig camera idx's own K and D for
 every output frame (allview.py:166-170): the raw photograph is kept, and the truth panel of frame idx is
-undistort.undistort_u8 of it on the host, csrc/undistort.hip's on the device."""
+undistort.undistort_u8 of it on the host, csrc/undistort.hip's on the device.
+A dataset opened with resize_frames at a scale other than 1 renders at the training size, and its
+truth panel -- built only under `show_truth` -- is dataset.truth_u8: to_8b_image of the Lanczos resize of the photograph."""
 import os
 import pickle
 
@@ -132,7 +134,8 @@ class ViewFrames:
             from PIL import Image
             if ds.resize_img_scale != 1.0:
                 raise NotImplementedError(f"{path}, frame {name}: the cameras have 'distortions' and resize_img_scale is "
-                                          f'{ds.resize_img_scale}: prescaled PNGs no longer match the stored intrinsics')
+                                          f'{ds.resize_img_scale}: prescaled PNGs no longer match the stored intrinsics, and '
+                                          "resizing a rig's undistorted photograph (train.resize_frames) is not built")
             self._D = np.asarray(cams[name]['distortions'], dtype=np.float64)
             if self._D.shape[0] < self.total_frames:
                 raise ValueError(f"{path}: frame {name} has {self._D.shape[0]} 'distortions', allview renders "
@@ -213,7 +216,10 @@ class ViewFrames:
         """Output frame idx as the reference's dict, numpy on the host (freeview.py:177-269 and its siblings)."""
         v, H, W, ds = self.view(idx), self.height, self.width, self.dataset
         out = host_frame(v['frame_name'], H, W, v['K'], v['E'], v['min'], v['max'], self.bgcolor)
-        if v['src'] is not None and self._D is None:
+        if v['src'] is not None and self._D is None and ds.resizing:
+            if self.truth:                                 # the photograph at the training size (dataset.truth_u8)
+                out['truth_u8'] = ds.truth_u8(v['src'])
+        elif v['src'] is not None and self._D is None:
             out['truth_u8'] = ds.images[v['src']]
         elif v['src'] is not None and self.truth:
             out['truth_u8'] = undistort_u8(self._raw, self._K[idx], self._D[idx])
@@ -255,7 +261,10 @@ class ViewFrames:
             consts = ds.constants(self._uploaded[i], device=True) if i in self._custom else ds.device_constants(v['src'])
             data.update({k: (torch.from_numpy(c) if isinstance(c, np.ndarray) else c) for k, c in consts.items()})
             meta = {'idx': i, 'ray_index': out['ray_index'], 'width': W, 'height': H, 'frame_name': v['frame_name']}
-            if v['src'] is not None and self._D is None:
+            if v['src'] is not None and self._D is None and ds.resizing:
+                if self.truth:                             # on the consumer's stream, like the gather
+                    meta['truth_u8'] = ds.truth_u8_device(v['src'])
+            elif v['src'] is not None and self._D is None:
                 meta['truth_u8'] = ds._dev['image'][v['src']]
             elif v['src'] is not None and self.truth:      # on the consumer's stream, like the gather
                 meta['truth_u8'] = ops.undistort_u8(self._raw_dev, None, self._K[i], self._D[i])[0]
