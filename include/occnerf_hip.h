@@ -794,6 +794,32 @@ int occnerf_progress_tile(const float *rgb, const int64_t *ray_index, int64_t R,
                           int32_t mosaic_rows, int32_t mosaic_cols, int32_t tile_x, int32_t tile_y, int32_t *partial,
                           int32_t *off_bg, void *stream);
 
+/* The body as a triangle mesh (occnerf_amd/mesh.py, run.py --type mesh).  The reference has no
+ * counterpart of these three entries: it exports no geometry.  Marching tetrahedra on the Kuhn split of every cube of
+ * field[nz][ny][nx] float32 (x fastest): six tetrahedra per cube around the body diagonal, one per permutation of the axes,
+ * so neighbouring cubes agree on every face diagonal and the surface is closed wherever it does not meet the grid's
+ * boundary.  A corner is inside iff f > level (strict, in float32: NaN is outside).  A surface vertex lies on one of the 7
+ * edge kinds that leave a grid point in a non-negative direction (3 axis edges, 3 face diagonals, the body diagonal) and is
+ * named by the int64 key lo_linear * 7 + kind, lo_linear = (z * ny + y) * nx + x, kind = dx + 2 dy + 4 dz - 1.
+ * Every axis has at least 2 points and nx * ny * nz < 2^31.  No atomics, no host wait; bit-identical to numpy. */
+
+/* No counterpart in the reference.  row_count[(nz-1)*(ny-1)] int32: the triangles of every row of cubes (z, y): 0, 1 or 2
+ * per tetrahedron, at most 12 per cube.  One workgroup per row. */
+int occnerf_mesh_count(const float *field, int32_t nx, int32_t ny, int32_t nz, float level, int32_t *row_count,
+                       void *stream);
+/* No counterpart in the reference.  row_start[(nz-1)*(ny-1)] int64: the exclusive prefix of row_count; T: its total.
+ * tri_keys[T,3] int64: the vertex keys of every triangle in the order (z, y, x, tetrahedron 0..5, triangle within the case),
+ * wound so that (b - a) x (c - a) points from inside to outside.  A row at or past T is never written.  T = 0 returns 0
+ * without a launch (tri_keys may then be NULL). */
+int occnerf_mesh_emit(const float *field, int32_t nx, int32_t ny, int32_t nz, float level, const int64_t *row_start,
+                      int64_t T, int64_t *tri_keys, void *stream);
+/* No counterpart in the reference.  keys[V] int64 (the welded keys) -> pos[V,3] float32: with a the key's lo point and b its
+ * other end in grid coordinates, t = (level - fa) / (fb - fa) and p = a + t * (b - a) in fp64, one rounding per operator, a t
+ * outside [0, 1] (only non-finite end values give one) replaced by 0.5; pos = float32(h_bbox_min + p * h).  h_bbox_min[3]:
+ * HOST, double.  A key that names no edge of the grid gives NaN and reads nothing.  V = 0 returns 0 without a launch. */
+int occnerf_mesh_vertices(const int64_t *keys, int64_t V, const float *field, int32_t nx, int32_t ny, int32_t nz,
+                          float level, const double *h_bbox_min, double h, float *pos, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

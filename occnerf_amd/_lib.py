@@ -143,6 +143,9 @@ SIGNATURES = {
     'occnerf_frame_metrics': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     'occnerf_progress_tile_blocks': (_i32, [_i32, _i32]),
     'occnerf_progress_tile': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'occnerf_mesh_count': (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp]),
+    'occnerf_mesh_emit': (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp, _vp]),
+    'occnerf_mesh_vertices': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, C.c_double, _vp, _vp]),
 }
 
 _lib = None

@@ -131,7 +131,13 @@ _DEFAULTS = {
     'knn_culling': True,             # cluster-culled exact kNN (False: brute force)
     'knn_center_cache': True,        # kNN queries within a proven radius of the frame's collapse point take its cached lists (same bits)
     'warp_bone_culling': True,       # warp kernel skips bones whose weight channel cannot reach a wave's samples (same bits)
+    # run.py --type mesh (occnerf_amd/mesh.py): resolution = voxels along the longest axis of the canonical box; level = the
+    # iso density, None: ln 2 / h (one voxel edge of matter half opaque); normals: write vertex normals; chunk: points per
+    # Network.query_canonical chunk
+    'mesh': {'resolution': 256, 'level': None, 'normals': True, 'chunk': 1 << 21},
 }
+# resolution + 1 points on the longest axis, at most as many on the others: the default grid stays below the kernels' 2^31
+assert (_DEFAULTS['mesh']['resolution'] + 1) ** 3 < 1 << 31
 
 _cfg = None
 

@@ -479,6 +479,55 @@ class Network(nn.Module):
         return (mask.view(-1, S) != 0).sum(dim=1)
 
     @torch.no_grad()
+    def query_canonical(self, xyz, chunk=1 << 21):
+        """raw[N,5] (rgb logits, density logit, signed distance) of the canonical field at xyz [N,3], float32 positions in
+        CANONICAL space on the module's device: neighbour search, features and the canonical MLP, the chain a frame's samples
+        run through after they have been warped.  No warp and no non-rigid offset is applied: the positions are taken as
+        canonical ones, which is what a mesh export wants (occnerf_amd/mesh.py).
+
+        Always the exact fp32 kernels, whatever cfg.mlp_precision says.  The points are evaluated `chunk` at a time (each
+        chunk padded to a multiple of 128 by repeating its last point, the padding dropped); every row is a function of its
+        own point alone, so the result does not depend on `chunk` bit for bit.  Nothing of the module changes: not its
+        train / eval mode, `point_counter`, the renderer's caches or any RNG state."""
+        if not torch.is_tensor(xyz) or not xyz.is_cuda:
+            raise RuntimeError('query_canonical: xyz must be a CUDA(HIP) tensor; there is no CPU path')
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
+            raise RuntimeError(f'query_canonical: xyz must be float32 [N,3], got {xyz.dtype} {tuple(xyz.shape)}')
+        if xyz.device != self.point_base.device:
+            raise RuntimeError(f'query_canonical: xyz is on {xyz.device}, the module on {self.point_base.device}')
+        chunk = int(chunk)
+        if chunk <= 0:
+            raise RuntimeError(f'query_canonical: chunk = {chunk} must be positive')
+        S = 128
+        chunk = -(-chunk // S) * S
+        N, dev = xyz.shape[0], xyz.device
+        raw = torch.empty(N, 5, device=dev)
+        if N == 0:
+            return raw
+        ctx = self._context()
+        enc = self.cnl_mlp.module.encoder
+        table = self._point_stage(ctx)                 # (this call's own: the renderer's cached constants are left alone)
+        base, counter = self.point_base.detach(), self.point_counter.detach()
+        pack = ops.point_pack(base, ctx['normals'], ctx['unit'], counter, table)
+        cw, cb = self.cnl_mlp.module.linear_params()
+        packed = ops.canonical_mlp_pack(cw, cb)
+        xyz = xyz.detach().contiguous()
+        for i in range(0, N, chunk):
+            n = min(chunk, N - i)
+            pad = (-n) % S
+            x = xyz[i:i + n]
+            if pad:
+                x = torch.cat([x, x[-1:].expand(pad, 3)]).contiguous()
+            knn = ops.msknn_clustered(x, (n + pad) // S, S, ctx['clusters'], ctx['seed'])
+            mlp_in, raw_c, _ = ops.sample_features(
+                x, knn, base, ctx['normals'], ctx['unit'], counter, table, ctx['bound32'], ctx['two_bound32'],
+                enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale, enc.base_resolution, pack=pack)
+            del knn
+            ops.canonical_mlp(mlp_in, packed, raw_c)
+            raw[i:i + n] = raw_c[:n]
+        return raw
+
+    @torch.no_grad()
     def render_preamble(self, data, iter_val=1e7):
         """(Rs[24,3,3], Ts[24,3], vol[25,G,G,G]) of a frame exactly as the render branch of `forward` computes them (the fused
         kernels of csrc/preamble.hip) -- for parity tools that feed a checker the same per-frame outputs."""

@@ -1284,3 +1284,65 @@ def resize_frame(image, mask, tables, bgcolor=None, out=None):
                                              _stream(mask))
     _lib.check(rc, 'resize_frame')
     return oi, oa
+
+
+# ------------------------------------------------------------------ the body as a triangle mesh
+def _mesh_field(who, field):
+    if not torch.is_tensor(field) or field.dim() != 3:
+        raise RuntimeError(f'{who}: field must be a [nz,ny,nx] tensor')
+    ptr = _chk(field, torch.float32, 'field')
+    nz, ny, nx = (int(s) for s in field.shape)
+    if min(nx, ny, nz) < 2 or nx * ny * nz >= 1 << 31:
+        raise RuntimeError(f'{who}: a {nx} x {ny} x {nz} grid: every axis needs 2 points, all of them fewer than 2^31')
+    return ptr, nx, ny, nz
+
+
+def mesh_count(field, level):
+    """Triangles of every row of cubes (z, y) of field [nz,ny,nx] float32 at the iso level (compared in float32; include/
+    occnerf_hip.h occnerf_mesh_count) -> int32 [(nz-1)*(ny-1)] on the device.  Nothing is read back here."""
+    ptr, nx, ny, nz = _mesh_field('mesh_count', field)
+    row_count = torch.empty((nz - 1) * (ny - 1), device=field.device, dtype=torch.int32)
+    with _guard(field):
+        rc = _lib.lib().occnerf_mesh_count(ptr, nx, ny, nz, float(np.float32(level)), row_count.data_ptr(), _stream(field))
+    _lib.check(rc, 'mesh_count')
+    return row_count
+
+
+def mesh_emit(field, level, row_start, T, out=None):
+    """The vertex keys of the T triangles (occnerf_mesh_emit): row_start int64 [(nz-1)*(ny-1)], the exclusive prefix of
+    mesh_count's result, T its total on the host -> tri_keys int64 [T,3] in the order (z, y, x, tetrahedron, triangle).
+    out: an int64 buffer of at least T rows of 3 to fill in place; rows at and past T are not written."""
+    ptr, nx, ny, nz = _mesh_field('mesh_emit', field)
+    T = int(T)
+    if T < 0:
+        raise RuntimeError(f'mesh_emit: T = {T} is negative')
+    ps = _chk(row_start, torch.int64, 'row_start')
+    if row_start.numel() != (nz - 1) * (ny - 1) or row_start.device != field.device:
+        raise RuntimeError(f'mesh_emit: row_start must be int64 [{(nz - 1) * (ny - 1)}] on the device of field')
+    if out is None:
+        out = torch.empty(T, 3, device=field.device, dtype=torch.int64)
+    po = _chk(out, torch.int64, 'tri_keys')
+    if out.numel() < 3 * T or out.device != field.device:
+        raise RuntimeError(f'mesh_emit: tri_keys must hold {T} rows of 3 on the device of field')
+    with _guard(field):
+        rc = _lib.lib().occnerf_mesh_emit(ptr, nx, ny, nz, float(np.float32(level)), ps, T, po if T else None, _stream(field))
+    _lib.check(rc, 'mesh_emit')
+    return out
+
+
+def mesh_vertices(keys, field, level, bbox_min, h):
+    """float32 [V,3] positions of the welded vertex keys (int64 [V], occnerf_mesh_vertices): the level's crossing on each
+    key's edge in fp64; bbox_min[3] and the voxel edge h on the host."""
+    ptr, nx, ny, nz = _mesh_field('mesh_vertices', field)
+    pk = _chk(keys, torch.int64, 'keys')
+    if keys.dim() != 1 or keys.device != field.device:
+        raise RuntimeError('mesh_vertices: keys must be int64 [V] on the device of field')
+    V = int(keys.numel())
+    pos = torch.empty(V, 3, device=field.device, dtype=torch.float32)
+    bmin = np.ascontiguousarray(np.asarray(bbox_min, dtype=np.float64).reshape(3))
+    with _guard(field):
+        rc = _lib.lib().occnerf_mesh_vertices(pk if V else None, V, ptr, nx, ny, nz, float(np.float32(level)),
+                                              bmin.ctypes.data_as(C.c_void_p), float(h), pos.data_ptr() if V else None,
+                                              _stream(field))
+    _lib.check(rc, 'mesh_vertices')
+    return pos

@@ -1,6 +1,6 @@
 """Render entry point with the reference's command line (run.py:246-247, configs/config.py:65-72):
 
-    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,backview,movement,allview,evaluate} [KEY VALUE ...]
+    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,backview,movement,allview,evaluate,mesh} [KEY VALUE ...]
 
 Frames go to experiments/<category>/<task>/<subject>/<experiment>/<load_net>/<folder>/NNNNNN.png
 exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seeded[:N]` renders the
@@ -199,8 +199,31 @@ def run_evaluate():
     _finish_ranks(rank, world)
 
 
+def run_mesh():
+    """The canonical body as a triangle mesh (occnerf_amd/mesh.py; the reference has no such type): the checkpoint loaded as
+    run_tpose loads it, the density on a grid over the canonical box the tpose frame of the configured source carries,
+    marching tetrahedra in HIP -> <logdir>/<load_net>/mesh/mesh.ply and mesh.json.  Rank 0 alone works."""
+    from occnerf_amd.mesh import export_mesh
+    cfg.ignore_non_rigid_motions = True
+    rank, world, model, loader, _, _ = _setup('tpose')
+    if rank == 0:
+        frame = next(iter(loader))
+        box = [np.asarray(torch.as_tensor(frame[k]).cpu().numpy(), dtype=np.float32).reshape(3)
+               for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz')]
+        bbox_max = np.asarray(torch.as_tensor(frame['cnl_bbox_max_xyz']).cpu().numpy(), dtype=np.float32).reshape(3) \
+            if 'cnl_bbox_max_xyz' in frame else (box[0] + np.float32(2.0) / box[1]).astype(np.float32)
+        m = cfg.mesh
+        out_dir = os.path.join(cfg.logdir, str(cfg.load_net).replace(':', '_'),
+                               'mesh' if not cfg.render_folder_name else cfg.render_folder_name)
+        info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
+                           normals=bool(m.normals), chunk=int(m.chunk))
+        print(f"mesh: {info['vertices']} vertices, {info['triangles']} triangles on a {info['grid_shape_xyz']} grid at level "
+              f"{info['level']:g} -> {os.path.join(out_dir, 'mesh.ply')}")
+    _finish_ranks(rank, world)
+
+
 if __name__ == '__main__':
     fn = globals().get(f'run_{args.type}')
     if fn is None:
-        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, backview, movement, allview, evaluate")
+        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, backview, movement, allview, evaluate, mesh")
     fn()
