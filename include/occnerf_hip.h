@@ -820,6 +820,20 @@ int occnerf_mesh_emit(const float *field, int32_t nx, int32_t ny, int32_t nz, fl
 int occnerf_mesh_vertices(const int64_t *keys, int64_t V, const float *field, int32_t nx, int32_t ny, int32_t nz,
                           float level, const double *h_bbox_min, double h, float *pos, void *stream);
 
+/* No counterpart in the reference.  The exported mesh in a frame's pose: x_c[V,3] float32 canonical
+ * positions -> p_out[V,3] float32 with F(p) = x_c, F the skeletal warp of occnerf_sample_warp in fp64 on the float32 Rs[nb,3,3],
+ * Ts[nb,3], vol[nb,G,G,G] (the background channel dropped) and the HOST h_bbox_min[3] / h_bbox_scale[3].  Per vertex: the bones
+ * with a positive trilinear weight at x_c by descending weight (ties: the lower index), at most `candidates` (1..8) of them;
+ * per candidate b a damped Newton iteration from R_b^T (x_c - T_b) with the analytic Jacobian, at most max_iter (1..255)
+ * steps, each the full step or its first halving (down to 1/32) that lowers max|F(p) - x_c|; converged when that is <= tol
+ * and the weight sum >= 1e-4.  flag[V] uint8: 0 converged, 1 not (p_out: the iterate with the smallest residual seen), 2 no
+ * bone has a weight at x_c (p_out = x_c); iters[V] uint8: Newton steps spent (saturating); resid[V] float32: max|F(p) - x_c| at
+ * the returned p before its rounding to float32.  One rounding per fp64 operator in a fixed order: a pure function of the
+ * inputs.  nb <= 32, 2 <= G <= 1024.  V = 0 returns 0 without a launch. */
+int occnerf_mesh_pose(const float *x_c, int64_t V, const float *Rs, const float *Ts, const float *vol, int32_t nb, int32_t G,
+                      const float *h_bbox_min, const float *h_bbox_scale, int32_t candidates, int32_t max_iter, double tol,
+                      float *p_out, uint8_t *flag, uint8_t *iters, float *resid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,11 @@ _DEFAULTS = {
     # iso density, None: ln 2 / h (one voxel edge of matter half opaque); normals: write vertex normals; chunk: points per
     # Network.query_canonical chunk
     'mesh': {'resolution': 256, 'level': None, 'normals': True, 'chunk': 1 << 21},
+    # run.py --type mesh, the mesh in the pose of frames (occnerf_amd/mesh.py export_posed): frames = None
+    # (canonical mesh only), a list of frame indices of the movement source, or 'all'; candidates / max_iter / tol = the bones
+    # tried per vertex, the Newton steps per bone and the residual (metres, on the fp64 iterate) that counts as converged;
+    # non_rigid: undo the frame's non-rigid offset too; world: write R(Rh) p + Th instead of the body's own space
+    'mesh_pose': {'frames': None, 'candidates': 3, 'max_iter': 20, 'tol': 1e-7, 'non_rigid': True, 'world': False},
 }
 # resolution + 1 points on the longest axis, at most as many on the others: the default grid stays below the kernels' 2^31
 assert (_DEFAULTS['mesh']['resolution'] + 1) ** 3 < 1 << 31

@@ -528,6 +528,45 @@ class Network(nn.Module):
         return raw
 
     @torch.no_grad()
+    def unoffset_canonical(self, x_c, data, iter_val=1e7, max_iter=10, tol=1e-6):
+        """(s [N,3], moving bool [N]): the skeletal-warp output s a frame maps onto the canonical positions x_c [N,3] (float32,
+        on the module's device), x_c = s + delta(s; pose) with the frame's non-rigid offset delta -- the fixed point s_0 = x_c,
+        s_{k+1} = x_c - delta(s_k), at most `max_iter` rounds or until no coordinate moves by more than `tol` (metres);
+        `moving` marks the rows that still did in the last round.  delta comes from the exact fp32 kernel of the renderer
+        (ops.nonrigid_rows) with the frame's condition vector and Hann window formed exactly as the render forms them, whatever
+        cfg.mlp_precision says.  With cfg.ignore_non_rigid_motions the render applies no offset: s = x_c bit for bit.
+        One host wait per round.  Like query_canonical it changes nothing about the module (it packs its own weights)."""
+        if not torch.is_tensor(x_c) or not x_c.is_cuda:
+            raise RuntimeError('unoffset_canonical: x_c must be a CUDA(HIP) tensor; there is no CPU path')
+        if x_c.dim() != 2 or x_c.shape[1] != 3 or x_c.dtype != torch.float32:
+            raise RuntimeError(f'unoffset_canonical: x_c must be float32 [N,3], got {x_c.dtype} {tuple(x_c.shape)}')
+        if x_c.device != self.point_base.device:
+            raise RuntimeError(f'unoffset_canonical: x_c is on {x_c.device}, the module on {self.point_base.device}')
+        cfg, dev, N = self.cfg, x_c.device, x_c.shape[0]
+        x_c = x_c.detach().contiguous()
+        moving = torch.zeros(N, device=dev, dtype=torch.bool)
+        if cfg.ignore_non_rigid_motions or N == 0:
+            return x_c.clone(), moving
+        nr = cfg.non_rigid_motion_mlp
+        hann = hann_window_weights(nr.multires, iter_val, nr.kick_in_iter, nr.full_band_iter).tolist()
+        posevec = data['dst_posevec'].detach().float().contiguous().to(dev).reshape(-1)
+        cond = posevec if iter_val >= nr.kick_in_iter else torch.zeros_like(posevec)
+        lin = [m for m in self.non_rigid_mlp.module.block_mlps if isinstance(m, nn.Linear)]
+        packed = ops.nonrigid_pack([m.weight.detach() for m in lin], [m.bias.detach() for m in lin])
+        w0, b0 = lin[0].weight.detach(), lin[0].bias.detach()
+        rows = torch.arange(N, device=dev, dtype=torch.int32)
+        count = torch.full((1,), N, device=dev, dtype=torch.int32)
+        s = x_c.clone()
+        for _ in range(int(max_iter)):
+            y = ops.nonrigid_rows(s.clone(), rows, count, cond, hann, w0, b0, packed)      # s + delta(s)
+            nxt = x_c - (y - s)
+            moving = (nxt - s).abs().amax(dim=1) > float(tol)
+            s = nxt
+            if not bool(moving.any()):
+                break
+        return s, moving
+
+    @torch.no_grad()
     def render_preamble(self, data, iter_val=1e7):
         """(Rs[24,3,3], Ts[24,3], vol[25,G,G,G]) of a frame exactly as the render branch of `forward` computes them (the fused
         kernels of csrc/preamble.hip) -- for parity tools that feed a checker the same per-frame outputs."""

@@ -1346,3 +1346,42 @@ def mesh_vertices(keys, field, level, bbox_min, h):
                                               _stream(field))
     _lib.check(rc, 'mesh_vertices')
     return pos
+
+
+def mesh_pose(x_c, Rs, Ts, vol, bbox_min, bbox_scale, candidates=3, max_iter=20, tol=1e-7):
+    """Observation-space positions of canonical points (occnerf_mesh_pose): x_c float32 [V,3], Rs [nb,3,3],
+    Ts [nb,3] and vol [>= nb,G,G,G] (only the first nb channels are read: the background channel is dropped) as
+    Network.render_preamble returns them, bbox_min[3] / bbox_scale[3] on the host -> (p float32 [V,3], flag uint8 [V],
+    iters uint8 [V], resid float32 [V]) on the device of x_c.  V = 0 launches nothing."""
+    px = _chk(x_c, torch.float32, 'mesh_pose: x_c')
+    if x_c.dim() != 2 or x_c.shape[1] != 3:
+        raise RuntimeError(f'mesh_pose: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    pR, pT, pv = _chk(Rs, torch.float32, 'mesh_pose: Rs'), _chk(Ts, torch.float32, 'mesh_pose: Ts'), _chk(vol, torch.float32, 'mesh_pose: vol')
+    nb = int(Rs.shape[0]) if Rs.dim() == 3 else -1
+    if nb < 1 or tuple(Rs.shape) != (nb, 3, 3) or tuple(Ts.shape) != (nb, 3):
+        raise RuntimeError(f'mesh_pose: Rs must be [nb,3,3] and Ts [nb,3], got {tuple(Rs.shape)} and {tuple(Ts.shape)}')
+    if vol.dim() != 4 or vol.shape[0] < nb or not (vol.shape[1] == vol.shape[2] == vol.shape[3]):
+        raise RuntimeError(f'mesh_pose: vol must be [>= {nb},G,G,G], got {tuple(vol.shape)}')
+    if not (Rs.device == Ts.device == vol.device == x_c.device):
+        raise RuntimeError('mesh_pose: x_c, Rs, Ts and vol must be on one device')
+    candidates, max_iter, tol = int(candidates), int(max_iter), float(tol)
+    if not 1 <= candidates <= 8:
+        raise RuntimeError(f'mesh_pose: candidates = {candidates} outside 1..8')
+    if not 1 <= max_iter <= 255:
+        raise RuntimeError(f'mesh_pose: max_iter = {max_iter} outside 1..255')
+    if not (0.0 <= tol < float('inf')):
+        raise RuntimeError(f'mesh_pose: tol = {tol} must be a finite number >= 0')
+    V, dev = int(x_c.shape[0]), x_c.device
+    p = torch.empty(V, 3, device=dev, dtype=torch.float32)
+    flag = torch.empty(V, device=dev, dtype=torch.uint8)
+    iters = torch.empty(V, device=dev, dtype=torch.uint8)
+    resid = torch.empty(V, device=dev, dtype=torch.float32)
+    if V == 0:
+        return p, flag, iters, resid
+    _kmin, pmin = _host_f32(bbox_min, 3)
+    _ksc, psc = _host_f32(bbox_scale, 3)
+    with _guard(x_c):
+        rc = _lib.lib().occnerf_mesh_pose(px, V, pR, pT, pv, nb, int(vol.shape[-1]), pmin, psc, candidates, max_iter, tol,
+                                          p.data_ptr(), flag.data_ptr(), iters.data_ptr(), resid.data_ptr(), _stream(x_c))
+    _lib.check(rc, 'mesh_pose')
+    return p, flag, iters, resid

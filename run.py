@@ -202,8 +202,10 @@ def run_evaluate():
 def run_mesh():
     """The canonical body as a triangle mesh (occnerf_amd/mesh.py; the reference has no such type): the checkpoint loaded as
     run_tpose loads it, the density on a grid over the canonical box the tpose frame of the configured source carries,
-    marching tetrahedra in HIP -> <logdir>/<load_net>/mesh/mesh.ply and mesh.json.  Rank 0 alone works."""
-    from occnerf_amd.mesh import export_mesh
+    marching tetrahedra in HIP -> <logdir>/<load_net>/mesh/mesh.ply and mesh.json.  With mesh_pose.frames set, also the mesh in
+    the pose of those frames of the movement source -> mesh/posed/<frame name>.ply and mesh/posed.json.  Rank 0 alone works."""
+    from occnerf_amd.mesh import PoseFrames, export_mesh, export_posed
+    ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
     cfg.ignore_non_rigid_motions = True
     rank, world, model, loader, _, _ = _setup('tpose')
     if rank == 0:
@@ -215,10 +217,24 @@ def run_mesh():
         m = cfg.mesh
         out_dir = os.path.join(cfg.logdir, str(cfg.load_net).replace(':', '_'),
                                'mesh' if not cfg.render_folder_name else cfg.render_folder_name)
+        mp = cfg.get('mesh_pose') or {}
+        posing = mp.get('frames') is not None
+        kept = {} if posing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
-                           normals=bool(m.normals), chunk=int(m.chunk))
+                           normals=bool(m.normals), chunk=int(m.chunk), keep=kept)
         print(f"mesh: {info['vertices']} vertices, {info['triangles']} triangles on a {info['grid_shape_xyz']} grid at level "
               f"{info['level']:g} -> {os.path.join(out_dir, 'mesh.ply')}")
+        if posing:
+            # the mesh in the pose of frames of the movement source: its body constants only
+            cfg.ignore_non_rigid_motions = ignore_non_rigid
+            source = PoseFrames(resolve_dataset_path(cfg, 'movement'), total_frames=int(cfg.render_frames),
+                                bbox_offset=float(cfg.bbox_offset), volume_size=int(cfg.mweight_volume.volume_size))
+            posed = export_posed(model, out_dir, kept, source, mp.frames, candidates=int(mp.candidates), max_iter=int(mp.max_iter),
+                                 tol=float(mp.tol), non_rigid=bool(mp.non_rigid), world=bool(mp.world), normals=bool(m.normals),
+                                 iter_val=cfg.eval_iter)
+            for f in posed['frames']:
+                print(f"posed {f['name']}: {f['not_converged']} not converged, {f['no_bone']} without a bone of {posed['vertices']} "
+                      f"vertices, worst residual {f['worst_resid']:.3g} m, {f['mean_iters']:.2f} Newton steps per vertex")
     _finish_ranks(rank, world)
 
 
