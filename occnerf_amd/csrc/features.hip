@@ -108,8 +108,10 @@ __global__ void point_sdf_backward_kernel(const float *__restrict__ point_cloud,
             dir[j][k] = (double)df[k];
             nbr[j][k] = (double)point_base[n * 3 + k];
         }
-        float na = norm3(df[0], df[1], df[2]);
-        nd[j] = (double)(na < 1e-8f ? 1e-8f : na);
+        // |dir| in fp64 like everything after it: the fp32 norm3 is off by up to u |dir|, which the terms of g below carry
+        // at full size while their sum cancels -- up to 300 x (u |g| + 64 2^-53 B) on a per-entry check
+        const double na = sqrt(dir[j][0] * dir[j][0] + dir[j][1] * dir[j][1] + dir[j][2] * dir[j][2]);
+        nd[j] = na < 1e-8 ? 1e-8 : na;
         c[j] = (dir[j][0] * unit[n * 3] + dir[j][1] * unit[n * 3 + 1] + dir[j][2] * unit[n * 3 + 2]) / nd[j];
         att[j] = fabs(c[j]);
         for (int k = 0; k < 3; k++) num[k] += att[j] * nbr[j][k];

@@ -465,6 +465,7 @@ def test_fused_adam_matches_torch(clip):
     assert sorted(sd_ref['state']) == sorted(sd_mine['state'])
     for k in sd_ref['state']:
         assert sorted(sd_ref['state'][k]) == sorted(sd_mine['state'][k])
+        assert _rel(sd_mine['state'][k]['exp_avg'], sd_ref['state'][k]['exp_avg']) <= 2e-6
         assert _rel(sd_mine['state'][k]['exp_avg_sq'], sd_ref['state'][k]['exp_avg_sq']) <= 2e-6
         assert float(sd_mine['state'][k]['step']) == float(sd_ref['state'][k]['step'])
 
