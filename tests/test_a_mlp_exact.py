@@ -12,7 +12,9 @@ beside the ordinary rows, which come out negative and positive; no infinities.  
 and its own exactness (fp32 sequential sum == float64 matrix product).  The sign of a zero sum does not depend on the
 order either: it is -0.0 only if every term is.  One exception, stated rather than hidden: the colour trunk's first
 layer cannot see -0.0 in the KERNEL -- its k-steps include the slot of `var`, which is not one of its inputs and is
-packed as a +0.0 weight -- so that layer is not asked for it.
+packed as a +0.0 weight -- so that layer is not asked for it.  The two direct-load kernels of mlp.hip and nonrigid.hip
+(`direct`) run the same cases, the 2^21 and the zero rows included, and need no further exception: their pad k-steps
+(+0.0 weights against +0.0 operands) do not change a bit of the outputs.
 """
 import numpy as np
 import pytest
@@ -24,6 +26,11 @@ from tests.gpu_util import DEV, T
 pytestmark = pytest.mark.gpu
 
 BIG = np.float32(2.0 ** 21)
+
+
+def _with_direct(sizes):
+    """every size for the LDS-staged kernel (id: the size) and again for the direct-load kernel (id: size-direct)"""
+    return [pytest.param(n, False, id=str(n)) for n in sizes] + [pytest.param(n, True, id='%d-direct' % n) for n in sizes]
 
 
 def _frac_bits(a):
@@ -160,13 +167,14 @@ def m16_case():
     return _m16_case()
 
 
-@pytest.mark.parametrize('n', M16_N)
-def test_canonical_mlp_exact(ops, m16_case, n):
-    """Bit-exact against the restatement; column 4 and the guard rows stay untouched (as test_canonical_mlp_ragged)."""
+@pytest.mark.parametrize('n,direct', _with_direct(M16_N))
+def test_canonical_mlp_exact(ops, m16_case, n, direct):
+    """Bit-exact against the restatement; column 4 and the guard rows stay untouched (as test_canonical_mlp_ragged).
+    direct: the 32-sample-wave direct-load kernel of mlp.hip (canonical_mlp_kernel) on the same case, 2^21 rows included."""
     x, Ws, Bs, want = m16_case
     packed = ops.canonical_mlp_pack([T(w) for w in Ws], [T(b) for b in Bs])
     raw = torch.full((n + 3, 5), 7.0, device=DEV)
-    ops.canonical_mlp(T(x[:n]), packed, raw[:n])
+    ops.canonical_mlp(T(x[:n]), packed, raw[:n], direct=direct)
     got = raw.cpu().numpy()
     bad = got[:n, :4].view(np.int32) != want[:n].view(np.int32)
     assert not bad.any(), (int(bad.sum()), got[:n, :4][bad][:4], want[:n][bad][:4])
@@ -226,14 +234,15 @@ def nr16_case():
     return _nr16_case()
 
 
-@pytest.mark.parametrize('n', NR16_N)
-def test_nonrigid_exact(ops, nr16_case, n):
+@pytest.mark.parametrize('n,direct', _with_direct(NR16_N))
+def test_nonrigid_exact(ops, nr16_case, n, direct):
+    """direct: the direct-load kernel of nonrigid.hip (nonrigid_kernel, ceil(N / 128) workgroups) on the same case"""
     cond, Ws, Bs, xyz, off = nr16_case
     Wd, Bd = [T(w) for w in Ws], [T(b) for b in Bs]
     packed = ops.nonrigid_pack(Wd, Bd)
     buf = torch.full((n + 2, 3), 5.0, device=DEV)
     buf[:n] = T(xyz[:n])
-    ops.nonrigid(buf[:n], T(cond), np.ones(6, np.float32), Wd[0], Bd[0], packed, out=buf[:n])
+    ops.nonrigid(buf[:n], T(cond), np.ones(6, np.float32), Wd[0], Bd[0], packed, out=buf[:n], direct=direct)
     got = buf.cpu().numpy()
     want = xyz[:n] + off[None]                         # one fp32 addition per coordinate, as the kernel's
     bad = got[:n].view(np.int32) != want.view(np.int32)
