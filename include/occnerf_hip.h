@@ -834,6 +834,34 @@ int occnerf_mesh_pose(const float *x_c, int64_t V, const float *Rs, const float 
                       const float *h_bbox_min, const float *h_bbox_scale, int32_t candidates, int32_t max_iter, double tol,
                       float *p_out, uint8_t *flag, uint8_t *iters, float *resid, void *stream);
 
+/* A triangle mesh seen through a pinhole camera (occnerf_amd/mesh_view.py, run.py --type mesh mesh_view.frames; DESIGN.md
+ * section 7j).  The reference has no counterpart of these three entries: it draws no geometry.  Bit-identical to
+ * tests/mesh_raster_restatement.py; the same bytes on every run.  Limits: 1 <= H, W <= 16384 and H * W <= 2^28; T, V < 2^31. */
+
+/* No counterpart in the reference.  pos[V,3] float32 -> xy[V,2] int32 (the projection in 1/256 pixel, ties to even), z[V]
+ * double (the camera-space depth), vflag[V] uint8, with the HOST h_K[9] (row-major 3x3; a skew K[0,1] != 0 is refused) and
+ * h_E[16] (row-major 4x4, the camera seen from the space of pos), in fp64, one rounding per operator: c = R p + t;
+ * u = fx (c_x / c_z) + cx, v alike.  vflag 1: not c_z >= 1e-3 (NaN included); 2: |256 u| or |256 v| above 2^22, or c_z above
+ * 2^20; a flagged vertex has xy = 0 and z = 0.  V = 0 returns 0 without a launch. */
+int occnerf_mesh_project(const float *pos, int64_t V, const double *h_K, const double *h_E, int32_t *xy, double *z,
+                         uint8_t *vflag, void *stream);
+/* No counterpart in the reference.  faces[T,3] int32 over the V projected vertices -> keys[H*W] uint64, IN/OUT: the caller
+ * sets every key to all ones (an empty pixel); every covered sample (pixel (i, j) is sampled at (256 j, 256 i); int64 edge
+ * functions, top-left rule, two-sided, nothing clipped) lowers its pixel's key to (bits of the float32 perspective-correct
+ * depth) << 32 | triangle index by an atomic minimum.  counts[7] int32, zeroed by the caller: triangles dropped for an index
+ * outside [0, V) / a vertex with vflag 1 / with vflag 2 / zero fixed-point area / a bounding box off the image, [5] the
+ * triangles with more than 64 samples in their clipped box, which a second launch draws with a wave each from wide_list[T]
+ * int32 (scratch), [6] is left to occnerf_mesh_resolve.  T = 0 or V = 0 returns 0 without a launch. */
+int occnerf_mesh_raster(const int32_t *faces, int64_t T, int64_t V, const int32_t *xy, const double *z, const uint8_t *vflag,
+                        int32_t H, int32_t W, uint64_t *keys, int32_t *wide_list, int32_t *counts, void *stream);
+/* No counterpart in the reference.  keys[H*W] -> cover[H*W] uint8, tri[H*W] int32 (-1: empty), depth[H*W] float32 (+inf:
+ * empty), rgb[H*W,3] uint8: the winner's colors[V,3] uint8 with perspective-correct weights, summed in vertex order and
+ * rounded to nearest even; the HOST h_bgcolor[3] uint8 where the pixel is empty.  counts[6] += the covered pixels.  T = 0 or
+ * V = 0 returns 0 without a launch (the caller fills the empty image). */
+int occnerf_mesh_resolve(const uint64_t *keys, const int32_t *faces, int64_t T, int64_t V, const int32_t *xy, const double *z,
+                         const uint8_t *vflag, const uint8_t *colors, const uint8_t *h_bgcolor, int32_t H, int32_t W,
+                         uint8_t *cover, int32_t *tri, float *depth, uint8_t *rgb, int32_t *counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

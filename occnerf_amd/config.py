@@ -140,6 +140,11 @@ _DEFAULTS = {
     # tried per vertex, the Newton steps per bone and the residual (metres, on the fp64 iterate) that counts as converged;
     # non_rigid: undo the frame's non-rigid offset too; world: write R(Rh) p + Th instead of the body's own space
     'mesh_pose': {'frames': None, 'candidates': 3, 'max_iter': 20, 'tol': 1e-7, 'non_rigid': True, 'world': False},
+    # run.py --type mesh, the posed mesh seen from its frame's camera (occnerf_amd/mesh_view.py export_views, DESIGN.md section
+    # 7j): frames = None (nothing happens), a list of frame indices of the movement source's prepared dataset, or 'all'; per
+    # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the
+    # mesh render beside the photograph.  The frames are posed with the mesh_pose keys
+    'mesh_view': {'frames': None, 'panels': True},
 }
 # resolution + 1 points on the longest axis, at most as many on the others: the default grid stays below the kernels' 2^31
 assert (_DEFAULTS['mesh']['resolution'] + 1) ** 3 < 1 << 31

@@ -1,0 +1,111 @@
+"""The posed mesh seen from the camera that photographed its frame, and held against that frame's mask (run.py --type mesh
+with mesh_view.frames).  The reference draws no geometry; this has no counterpart there.
+
+  rasterize      a triangle mesh through a pinhole camera in HIP (csrc/mesh_raster.hip: project, raster, resolve): per pixel
+                 coverage, the nearest triangle, its depth and its interpolated vertex colour.  Screen positions are snapped to
+                 1/256 pixel, coverage is integer arithmetic with the top-left fill rule and the depth merge is a 64-bit minimum,
+                 so the image is a pure function of its inputs: tests/mesh_raster_restatement.py states it in numpy, and the
+                 kernels give its bytes on every run.  Pixel (row i, column j) is sampled at (u, v) = (j, i), where the
+                 renderer's rays (synth.get_rays_from_KRT) leave the camera, so the silhouette, the masks and the renderer's
+                 alpha map speak about the same pixels;
+  silhouette_iou the silhouette against gt_alpha > 0.5 (eval.py's threshold for the ground-truth silhouette): exact integers;
+  export_views   per frame of a prepared dataset: the posed mesh (mesh.pose_mesh, in the body's own space) through the frame's K
+                 and body-space E -> view/<frame name>.png, the mesh beside the photograph, and view.json.
+
+Not offered: clipping at the near plane (a triangle with a vertex nearer than a millimetre is dropped and counted),
+anti-aliasing, lighting and textures, a comparison of the silhouette with the *rendered* alpha map, and the all_cameras.pkl
+rig."""
+import json
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import ops
+
+COUNTS = ops.MESH_RASTER_COUNTS
+
+
+def rasterize(verts, faces, colors, K, E, H, W, bgcolor=(255, 255, 255), faces_checked=False):
+    """verts float32 [V,3], faces int32 [T,3] and colors uint8 [V,3] on one GPU; K 3x3 and E 4x4 (the camera seen from the space
+    of verts) on the host; bgcolor 0..255 -> a dict of device tensors: xy int32 [V,2], z float64 [V], vflag uint8 [V], cover
+    uint8 [H,W], tri int32 [H,W] (-1 where empty), depth float32 [H,W] (+inf where empty), rgb uint8 [H,W,3] and counts int32
+    [7] in the order COUNTS (triangles dropped per reason, triangles of the wide pass, pixels covered).  Nothing is read back."""
+    xy, z, vflag = ops.mesh_project(verts, K, E)
+    keys, counts = ops.mesh_raster(faces, xy, z, vflag, H, W, faces_checked=faces_checked)
+    cover, tri, depth, rgb = ops.mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor)
+    return {'xy': xy, 'z': z, 'vflag': vflag, 'cover': cover, 'tri': tri, 'depth': depth, 'rgb': rgb, 'counts': counts}
+
+
+def silhouette_iou(cover, gt_alpha):
+    """cover uint8 [H,W] and gt_alpha float32 [H,W] on one device -> (intersection, union, IoU, covered, inside share): integer
+    counts, IoU = I / U in float64 (None when the union is empty), the share of the covered pixels that lie inside the mask
+    (None when nothing is covered).  One blocking copy of three integers."""
+    a, b = cover > 0, gt_alpha > 0.5
+    inter, union, covered = (int(v) for v in torch.stack([(a & b).sum(), (a | b).sum(), a.sum()]).tolist())
+    return inter, union, (inter / union if union else None), covered, (inter / covered if covered else None)
+
+
+def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, panels=True,
+                 bgcolor=(255., 255., 255.), iter_val=1e7):
+    """<out_dir>/view/<frame name>.png (panels: the mesh render beside the photograph) for the frames (indices into `dataset`,
+    a dataset.PreparedDataset; 'all': every one) and <out_dir>/view.json -> its dict.  kept: what export_mesh(keep=...) left of
+    mesh.ply.  Every frame is posed here, in memory, as mesh.export_posed poses it (the same call, the same bits)."""
+    from .image import ImageWriter
+    from .mesh import _POSE_KEYS, pose_mesh
+    if dataset is None:
+        raise RuntimeError('mesh_view.frames: the silhouette is held against the masks of a prepared dataset; the synthetic frame '
+                           'source has none (set train.dataset_path or movement.dataset)')
+    dev = net.point_base.device
+    idxs = list(range(len(dataset))) if isinstance(frames, str) and frames == 'all' else [int(i) for i in frames]
+    for i in idxs:
+        if not 0 <= i < len(dataset):
+            raise RuntimeError(f'mesh_view.frames: frame {i} outside the {len(dataset)} frames of the dataset')
+    verts = kept['verts']
+    V, T = int(verts.shape[0]), int(np.asarray(kept['faces']).shape[0])
+    f_host = np.ascontiguousarray(np.asarray(kept['faces'], dtype=np.int32).reshape(-1, 3))
+    if T and (f_host.min() < 0 or f_host.max() >= V):
+        raise RuntimeError(f'mesh_raster: face index outside [0, {V})')
+    faces = torch.from_numpy(f_host).to(dev)
+    colors = torch.from_numpy(np.ascontiguousarray(np.asarray(kept['colors'], dtype=np.uint8).reshape(-1, 3))).to(dev)
+    H, W = int(dataset.height), int(dataset.width)
+    os.makedirs(out_dir, exist_ok=True)
+    writer = ImageWriter(output_dir=out_dir, exp_name='view') if panels else None
+
+    def clock():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    per_frame = []
+    for i in idxs:
+        f = dataset.frames[i]
+        fr = dataset.host_constants(i)
+        data = {k: torch.from_numpy(np.ascontiguousarray(fr[k])).to(dev) for k in _POSE_KEYS}
+        data.update({k: np.asarray(fr[k], dtype=np.float32) for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz')})
+        stats = {}
+        p, flag, _, _ = pose_mesh(net, verts, data, candidates, max_iter, tol, non_rigid, iter_val, stats)
+        t0 = clock()
+        r = rasterize(p, faces, colors, f['K'], f['E'], H, W, bgcolor, faces_checked=True)
+        t1 = clock()
+        gt = torch.from_numpy(np.ascontiguousarray(dataset.gt_alpha(i))).to(dev)
+        inter, union, iou, covered, inside = silhouette_iou(r['cover'], gt)
+        counts = r['counts'].tolist()
+        flagged = int((flag != 0).sum().item())
+        t2 = clock()
+        if writer is not None:
+            truth = torch.from_numpy(np.ascontiguousarray(dataset.truth_u8(i))).to(dev)
+            writer.append_device(torch.cat([r['rgb'], truth], dim=1), img_name=f['frame_name'])
+        stats['seconds'].update(raster=round(t1 - t0, 4), compare=round(t2 - t1, 4))
+        per_frame.append({'frame': i, 'name': f['frame_name'], 'iou': iou, 'intersection': inter, 'union': union,
+                          'covered': covered, 'inside_share': inside,
+                          'dropped': dict(zip(COUNTS[:5], counts[:5])), 'wide': counts[5], 'posing_flagged': flagged,
+                          'seconds': stats['seconds']})
+    if writer is not None:
+        writer.finalize()
+    ious = [f['iou'] for f in per_frame if f['iou'] is not None]
+    info = {'vertices': V, 'triangles': T, 'height': H, 'width': W, 'mask_threshold': 0.5,
+            'mean_iou': float(np.mean(ious)) if ious else None, 'frames': per_frame}
+    with open(os.path.join(out_dir, 'view.json'), 'w') as out:
+        json.dump(info, out, indent=1)
+        out.write('\n')
+    return info

@@ -1385,3 +1385,113 @@ def mesh_pose(x_c, Rs, Ts, vol, bbox_min, bbox_scale, candidates=3, max_iter=20,
                                           p.data_ptr(), flag.data_ptr(), iters.data_ptr(), resid.data_ptr(), _stream(x_c))
     _lib.check(rc, 'mesh_pose')
     return p, flag, iters, resid
+
+
+# ------------------------------------------------------------------ the mesh seen through a camera
+MESH_RASTER_COUNTS = ('index', 'near', 'guard', 'area', 'offscreen', 'wide', 'covered')
+MESH_RASTER_MAX_SIDE, MESH_RASTER_MAX_PIXELS = 16384, 1 << 28
+
+
+def _host_matrix64(vals, shape, name):
+    a = np.ascontiguousarray(np.asarray(vals.detach().cpu().numpy() if torch.is_tensor(vals) else vals, dtype=np.float64))
+    if a.shape != shape:
+        raise RuntimeError(f'{name} must be {shape[0]}x{shape[1]}, got {a.shape}')
+    return a
+
+
+def mesh_project(pos, K, E):
+    """Vertices through a pinhole camera (occnerf_mesh_project): pos float32 [V,3] on the device, K 3x3 and E 4x4 on the host
+    (float64; E is the camera seen from the space of pos) -> (xy int32 [V,2] in 1/256 pixel, z float64 [V], vflag uint8 [V]: 1
+    nearer than a millimetre, 2 past the guard band).  V = 0 launches nothing."""
+    pp = _chk(pos, torch.float32, 'mesh_project: pos')
+    if pos.dim() != 2 or pos.shape[1] != 3:
+        raise RuntimeError(f'mesh_project: pos must be float32 [V,3], got {tuple(pos.shape)}')
+    K, E = _host_matrix64(K, (3, 3), 'mesh_project: K'), _host_matrix64(E, (4, 4), 'mesh_project: E')
+    if K[0, 1] != 0.0:
+        raise NotImplementedError(f'mesh_project: skew K[0,1] = {K[0, 1]!r} is not built')
+    V, dev = int(pos.shape[0]), pos.device
+    if V >= 1 << 31:
+        raise RuntimeError(f'mesh_project: V = {V} reaches the limit of 2^31')
+    xy = torch.empty(V, 2, device=dev, dtype=torch.int32)
+    z = torch.empty(V, device=dev, dtype=torch.float64)
+    vflag = torch.empty(V, device=dev, dtype=torch.uint8)
+    if V == 0:
+        return xy, z, vflag
+    with _guard(pos):
+        rc = _lib.lib().occnerf_mesh_project(pp, V, K.ctypes.data_as(C.c_void_p), E.ctypes.data_as(C.c_void_p), xy.data_ptr(),
+                                             z.data_ptr(), vflag.data_ptr(), _stream(pos))
+    _lib.check(rc, 'mesh_project')
+    return xy, z, vflag
+
+
+def _mesh_raster_args(who, faces, xy, z, vflag, H, W):
+    pf = _chk(faces, torch.int32, f'{who}: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f'{who}: faces must be int32 [T,3], got {tuple(faces.shape)}')
+    px, pz, pv = _chk(xy, torch.int32, f'{who}: xy'), _chk(z, torch.float64, f'{who}: z'), _chk(vflag, torch.uint8, f'{who}: vflag')
+    V = int(vflag.numel())
+    if tuple(xy.shape) != (V, 2) or tuple(z.shape) != (V,) or not (xy.device == z.device == vflag.device == faces.device):
+        raise RuntimeError(f'{who}: xy [V,2], z [V] and vflag [V] must be mesh_project\'s, on the device of faces')
+    H, W = int(H), int(W)
+    if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE and H * W <= MESH_RASTER_MAX_PIXELS):
+        raise RuntimeError(f'{who}: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE} or more than 2^28 pixels')
+    T = int(faces.shape[0])
+    if T >= 1 << 31 or V >= 1 << 31:
+        raise RuntimeError(f'{who}: T = {T} / V = {V} reaches the limit of 2^31')
+    return pf, px, pz, pv, T, V, H, W
+
+
+def mesh_raster(faces, xy, z, vflag, H, W, faces_checked=False):
+    """Triangles into the per-pixel keys (occnerf_mesh_raster): faces int32 [T,3] and mesh_project's xy / z / vflag on one
+    device -> (keys int64 [H,W]: the bits of (float32 depth) << 32 | triangle index of the nearest covering triangle, -1 (all
+    ones) where there is none; counts int32 [7] in the order MESH_RASTER_COUNTS, 'covered' still 0).  A face index outside
+    [0, V) is refused by name before anything is launched (one blocking read of the faces' extremes; faces_checked=True: the
+    caller has made that test); the kernels themselves never use one as an address.  T = 0 or V = 0 launches nothing."""
+    pf, px, pz, pv, T, V, H, W = _mesh_raster_args('mesh_raster', faces, xy, z, vflag, H, W)
+    if T and not faces_checked:
+        lo, hi = int(faces.min().item()), int(faces.max().item())
+        if lo < 0 or hi >= V:
+            raise RuntimeError(f'mesh_raster: face index {lo if lo < 0 else hi} outside [0, {V})')
+    dev = faces.device
+    keys = torch.full((H, W), -1, device=dev, dtype=torch.int64)
+    counts = torch.zeros(len(MESH_RASTER_COUNTS), device=dev, dtype=torch.int32)
+    if T == 0 or V == 0:
+        return keys, counts
+    wide_list = torch.empty(T, device=dev, dtype=torch.int32)
+    with _guard(faces):
+        rc = _lib.lib().occnerf_mesh_raster(pf, T, V, px, pz, pv, H, W, keys.data_ptr(), wide_list.data_ptr(), counts.data_ptr(),
+                                            _stream(faces))
+    _lib.check(rc, 'mesh_raster')
+    return keys, counts
+
+
+def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
+    """The image of mesh_raster's keys (occnerf_mesh_resolve): colors uint8 [V,3] on the device, bgcolor 3 values 0..255 on the
+    host -> (cover uint8 [H,W], tri int32 [H,W] (-1 empty), depth float32 [H,W] (+inf empty), rgb uint8 [H,W,3]); counts[6]
+    receives the covered pixels.  T = 0 or V = 0 launches nothing: the empty image."""
+    pk = _chk(keys, torch.int64, 'mesh_resolve: keys')
+    if keys.dim() != 2:
+        raise RuntimeError(f'mesh_resolve: keys must be int64 [H,W], got {tuple(keys.shape)}')
+    H, W = (int(s) for s in keys.shape)
+    pf, px, pz, pv, T, V, H, W = _mesh_raster_args('mesh_resolve', faces, xy, z, vflag, H, W)
+    pn = _chk(counts, torch.int32, 'mesh_resolve: counts')
+    if counts.numel() != len(MESH_RASTER_COUNTS) or counts.device != faces.device or keys.device != faces.device:
+        raise RuntimeError(f'mesh_resolve: keys and counts int32 [{len(MESH_RASTER_COUNTS)}] must be mesh_raster\'s')
+    pc = _chk(colors, torch.uint8, 'mesh_resolve: colors')
+    if tuple(colors.shape) != (V, 3) or colors.device != faces.device:
+        raise RuntimeError(f'mesh_resolve: colors must be uint8 [{V},3] on the device of faces, got {tuple(colors.shape)}')
+    bg = np.ascontiguousarray(np.clip(np.rint(np.asarray(bgcolor, dtype=np.float64).reshape(3)), 0, 255).astype(np.uint8))
+    dev = faces.device
+    if T == 0 or V == 0:
+        return (torch.zeros(H, W, device=dev, dtype=torch.uint8), torch.full((H, W), -1, device=dev, dtype=torch.int32),
+                torch.full((H, W), float('inf'), device=dev, dtype=torch.float32),
+                torch.from_numpy(bg).to(dev).expand(H, W, 3).contiguous())
+    cover = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    tri = torch.empty(H, W, device=dev, dtype=torch.int32)
+    depth = torch.empty(H, W, device=dev, dtype=torch.float32)
+    rgb = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    with _guard(faces):
+        rc = _lib.lib().occnerf_mesh_resolve(pk, pf, T, V, px, pz, pv, pc, bg.ctypes.data_as(C.c_void_p), H, W, cover.data_ptr(),
+                                             tri.data_ptr(), depth.data_ptr(), rgb.data_ptr(), pn, _stream(faces))
+    _lib.check(rc, 'mesh_resolve')
+    return cover, tri, depth, rgb

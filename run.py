@@ -4,7 +4,9 @@
 
 Frames go to experiments/<category>/<task>/<subject>/<experiment>/<load_net>/<folder>/NNNNNN.png
 exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seeded[:N]` renders the
-seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on disk.
+seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on disk.  `--type mesh` writes no frames but
+<...>/<load_net>/mesh/mesh.ply and mesh.json; with `mesh_pose.frames` also mesh/posed/<frame name>.ply and mesh/posed.json;
+with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json (run_mesh below).
 
 Several GPUs: start it under torchrun, one process per GPU --
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run.py --cfg ... --type movement
@@ -203,7 +205,10 @@ def run_mesh():
     """The canonical body as a triangle mesh (occnerf_amd/mesh.py; the reference has no such type): the checkpoint loaded as
     run_tpose loads it, the density on a grid over the canonical box the tpose frame of the configured source carries,
     marching tetrahedra in HIP -> <logdir>/<load_net>/mesh/mesh.ply and mesh.json.  With mesh_pose.frames set, also the mesh in
-    the pose of those frames of the movement source -> mesh/posed/<frame name>.ply and mesh/posed.json.  Rank 0 alone works."""
+    the pose of those frames of the movement source -> mesh/posed/<frame name>.ply and mesh/posed.json.  With mesh_view.frames
+    set, also the posed mesh seen from the camera of those frames of the movement source's prepared dataset (occnerf_amd/
+    mesh_view.py) -> mesh/view/<frame name>.png, the mesh beside the photograph, and mesh/view.json with
+    the silhouette's IoU against the frame's mask.  Rank 0 alone works."""
     from occnerf_amd.mesh import PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
     cfg.ignore_non_rigid_motions = True
@@ -219,7 +224,12 @@ def run_mesh():
                                'mesh' if not cfg.render_folder_name else cfg.render_folder_name)
         mp = cfg.get('mesh_pose') or {}
         posing = mp.get('frames') is not None
-        kept = {} if posing else None
+        mv = cfg.get('mesh_view') or {}
+        viewing = mv.get('frames') is not None
+        if viewing and resolve_dataset_path(cfg, 'movement') is None:
+            raise SystemExit('mesh_view.frames: the silhouette is held against the masks of a prepared dataset; the synthetic frame '
+                             'source has none (set train.dataset_path or movement.dataset)')
+        kept = {} if posing or viewing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
                            normals=bool(m.normals), chunk=int(m.chunk), keep=kept)
         print(f"mesh: {info['vertices']} vertices, {info['triangles']} triangles on a {info['grid_shape_xyz']} grid at level "
@@ -235,6 +245,23 @@ def run_mesh():
             for f in posed['frames']:
                 print(f"posed {f['name']}: {f['not_converged']} not converged, {f['no_bone']} without a bone of {posed['vertices']} "
                       f"vertices, worst residual {f['worst_resid']:.3g} m, {f['mean_iters']:.2f} Newton steps per vertex")
+        if viewing:
+            # the posed mesh through each frame's own camera, against the frame's mask: the dataset as
+            # --type movement opens it, so K, the mask and the photograph are those of the training size
+            from occnerf_amd.dataset import PreparedDataset
+            from occnerf_amd.mesh_view import export_views
+            cfg.ignore_non_rigid_motions = ignore_non_rigid
+            dev = torch.device('cuda', torch.cuda.current_device())
+            dataset = PreparedDataset.from_cfg(cfg, resolve_dataset_path(cfg, 'movement'), device=None, prepare_device=dev)
+            views = export_views(model, out_dir, kept, dataset, mv.frames, candidates=int(mp.get('candidates', 3)),
+                                 max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
+                                 non_rigid=bool(mp.get('non_rigid', True)), panels=bool(mv.get('panels', True)),
+                                 bgcolor=cfg.bgcolor, iter_val=cfg.eval_iter)
+            for f in views['frames']:
+                iou = 'none (empty union)' if f['iou'] is None else f"{f['iou']:.4f}"
+                print(f"view {f['name']}: IoU {iou} ({f['intersection']} / {f['union']} pixels), {f['covered']} pixels covered, "
+                      f"{sum(f['dropped'].values())} of {views['triangles']} triangles dropped, {f['posing_flagged']} vertices "
+                      f"flagged by the posing")
     _finish_ranks(rank, world)
 
 
