@@ -16,6 +16,8 @@ namespace occ {
 constexpr int kWave = 64;       // CDNA wavefront
 constexpr int kNumCU = 256;     // MI355X
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 void set_error(const char *fmt, ...);
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }

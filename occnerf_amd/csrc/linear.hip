@@ -34,6 +34,7 @@
 // 2-byte reads per operand per MFMA (the LDS port, not the matrix pipe, paces that loop -- still under the HBM
 // time of the tile).  Column sums of dZ (the bias gradient) ride along in the waves that own k-block 0.
 #include "common.h"
+#include "weight_ring.h"
 
 namespace occ {
 namespace lin {
@@ -241,15 +242,9 @@ __global__ __launch_bounds__(256, 2) void linear_kernel(const LinearArgs a) {
             for (int it = 0; it < NB * 2; it++) {
                 const int rb = wave * (NB * 8) + it * 4;                       // wave-uniform first row
                 const int g = (lane & 15) ^ ((rb + (lane >> 4)) & 15);
-                if (g < ppr) {
-                    unsigned keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                                 "s_mov_b32 m0, %0"
-                                 : "=&s"(keep)
-                                 : "v"((unsigned)((lane >> 4) * (int)ldw + g * 16)), "s"(a.W + rb * ldw + wcol + c0),
-                                   "s"(wl_lds + (unsigned)(rb * kChunkBytes))
-                                 : "memory");
-                }
+                if (g < ppr)
+                    glds16(a.W + rb * ldw + wcol + c0, (unsigned)((lane >> 4) * (int)ldw + g * 16),
+                           wl_lds + (unsigned)(rb * kChunkBytes));
             }
             u32x4 xf[8];
 #pragma unroll

@@ -28,6 +28,7 @@
 #include "common.h"
 #include "mlp_layout.h"
 #include "split.h"
+#include "weight_ring.h"
 
 namespace occ {
 
@@ -428,18 +429,15 @@ __global__ __launch_bounds__(256, 1) void canonical_mlp_bf16x3_kernel(
 // bf16x3, LDS-staged weights.  The direct-load kernel above makes each of the 4 waves of a
 // workgroup pull the whole 1.8 MB weight stream through L1 itself (85 B/clk/CU against a
 // 64 B/clk L1): it runs at ~40 % of the bf16 pipe.  Here the stream is cut into 16 KiB chunks
-// (one 16-wide k-step x {hi,lo} x 8 output blocks) that the workgroup fetches ONCE with
-// LDS-DMA (global_load_lds_dwordx4, 4 x 1 KiB per wave per chunk) into a 4-slot ring and all
-// four waves read with ds_read_b128.  One raw s_barrier per chunk; the DMA of chunks g+1..g+3
-// stays in flight across it behind a counted s_waitcnt vmcnt(8) (hipcc would drain to
-// vmcnt(0) before the first ds_read if the DMA were a builtin it can see, so the DMA is inline
-// asm and the wait is placed by hand).  Biases and the VALU head rows are copied to LDS once.
+// (one 16-wide k-step x {hi,lo} x 8 output blocks) that the workgroup fetches ONCE through the
+// LDS-DMA ring of weight_ring.h (4 x 1 KiB per wave per chunk) and all four waves read with
+// ds_read_b128.  Biases and the VALU head rows are copied to LDS once.
 // ---------------------------------------------------------------------------------------
-constexpr int kRingSlots = 4;
 constexpr int kChunkUnits = 1024;                                  // 16-byte units per chunk
+typedef WeightRing<kChunkUnits, kChunkUnits / 64 / 4> SplitRing;
 constexpr int kChunksTotal = kS_L0Geo + 3 * kS_Hidden + kS_Hidden / 4 + kS_L0Rgb + 3 * kS_Hidden;
 static_assert(BlobH::kTotal == (int64_t)kChunksTotal * kChunkUnits, "bf16 blob is the chunk stream");
-constexpr int kTailChunks = kRingSlots - 1;                        // zero chunks the prefetch may touch
+constexpr int kTailChunks = SplitRing::kAhead;              // (a chunk is entered when it is multiplied, not before)
 
 // fp32 side data in LDS (floats): biases in accumulator order + the dot-row weights
 struct Aux {
@@ -478,10 +476,8 @@ __global__ __launch_bounds__(256, 1) void canonical_mlp_split_lds_kernel(
     constexpr float kSx = P::kSx, kInvSx = 1.0f / P::kSx;
     const int64_t N = n_dev ? (int64_t)*n_dev : N_max;
     if ((int64_t)blockIdx.x * 128 >= N) return;      // launches are sized for the worst case; uniform per workgroup
-    // ONE __shared__ object (a second one makes hipcc drain vmcnt before every ds_read)
-    __shared__ __attribute__((aligned(16))) V8 smem[kRingSlots * kChunkUnits + Aux::kTotal / 4];
-    V8 *ring = smem;
-    float *aux = reinterpret_cast<float *>(smem + kRingSlots * kChunkUnits);
+    __shared__ __attribute__((aligned(16))) V8 smem[SplitRing::kLdsUnits + Aux::kTotal / 4];      // [ring | aux]
+    float *aux = reinterpret_cast<float *>(smem + SplitRing::kLdsUnits);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -522,27 +518,19 @@ __global__ __launch_bounds__(256, 1) void canonical_mlp_split_lds_kernel(
     }
     __syncthreads();
 
-    // ---- weight stream: chunk g lives in ring slot g & 3 ----
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) V8 *)ring;
-    auto issue = [&](int g) {      // this wave's quarter of chunk g: 4 x 1 KiB
-#pragma unroll
-        for (int f = 0; f < 4; f++) {
-            const int frag = wave * 4 + f;
-            glds16(pkh + (size_t)g * kChunkUnits + frag * 64, lane * 16,
-                   ring_lds + (unsigned)(((g & (kRingSlots - 1)) * kChunkUnits + frag * 64) * 16));
-        }
-    };
+    // ---- weight stream (weight_ring.h): chunk g lives in ring slot g & 3 ----
+    const SplitRing ring(pkh, smem, wave, lane);
     int g = 0;                     // next chunk to consume
-    issue(0);
-    issue(1);
-    issue(2);
+    ring.chunk(0, 0);
+    ring.chunk(1, 1);
+    ring.chunk(2, 2);
 
-    // wait for chunk g (own quarter), rendezvous, refill the slot freed by chunk g-1
+    // enter chunk g and refill the slot freed by chunk g-1 at once (the geometry head)
 #define OCC_CHUNK_ENTER()                                              \
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                   \
+    SplitRing::wait_oldest();                                          \
     __builtin_amdgcn_s_barrier();                                      \
-    issue(g + 3);                                                      \
-    const V8 *slot_ = ring + (g & (kRingSlots - 1)) * kChunkUnits; \
+    ring.chunk(g + 3, g + 3);                                          \
+    const V8 *slot_ = ring.slot<V8>(g);                                \
     g++;
 
     // The four LDS-DMA pieces of the refill are not issued
@@ -550,22 +538,17 @@ __global__ __launch_bounds__(256, 1) void canonical_mlp_split_lds_kernel(
     // MI355X_MICROARCH.md), but one by one in the second half of the k-step's MFMAs.  Measured with s_memtime stamps
     // (profiles/r05_split_kernel_phases.md): a hidden layer 17.5 K instead of 19.0 K cycles, a tile 147.7 K instead of 153.5 K,
     // the launch 39.8 instead of 40.3 ms -- two thirds of the cycles saved come back as a lower clock
-    auto issue_piece = [&](int g, int f) {
-        const int frag = wave * 4 + f;
-        glds16(pkh + (size_t)g * kChunkUnits + frag * 64, lane * 16,
-               ring_lds + (unsigned)(((g & (kRingSlots - 1)) * kChunkUnits + frag * 64) * 16));
-    };
 #define OCC_PIECE(F)                                    \
     __builtin_amdgcn_sched_barrier(0);                  \
-    issue_piece(g + 2, F);                              \
+    ring.piece(g + 2, g + 2, F);                        \
     __builtin_amdgcn_sched_barrier(0);
 
     // one 16-wide k-step per chunk, 8 output blocks
 #define OCC_LAYER_LDS8(STEPS, ACC, BOPS)                                                   \
     _Pragma("unroll") for (int s_ = 0; s_ < (STEPS); s_++) {                               \
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                               \
+            SplitRing::wait_oldest();                                                      \
             __builtin_amdgcn_s_barrier();                                                  \
-            const V8 *slot_ = ring + (g & (kRingSlots - 1)) * kChunkUnits;                 \
+            const V8 *slot_ = ring.slot<V8>(g);                                            \
             g++;                                                                           \
             V8 ah_[kOB], al_[kOB];                                                         \
             _Pragma("unroll") for (int ob_ = 0; ob_ < kOB; ob_++) ah_[ob_] = slot_[ob_ * 64 + lane];         \
@@ -665,7 +648,7 @@ __global__ __launch_bounds__(256, 1) void canonical_mlp_split_lds_kernel(
         OCC_LAYER_LDS8(kS_Hidden, acc, BOPS_ACT)
         if (l < 2) relu_split<P, WATCH>(bact, acc, amax);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the 3 tail chunks: nobody reads them
+    SplitRing::drain();      // the 3 tail chunks: nobody reads them
     float rgb[3];
 #pragma unroll
     for (int c = 0; c < 3; c++) {

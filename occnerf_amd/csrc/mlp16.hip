@@ -5,11 +5,10 @@
 // and TWO waves fit per SIMD (the 32-sample kernel in mlp.hip needs 128 + 128 and runs one): the second
 // wave's MFMAs cover the first one's bias/ReLU epilogue, barriers and LDS latency.  Halving the samples
 // per wave doubles the weight bytes per sample, so the weights cannot come through L1 any more (measured:
-// 232 ms); the workgroup fetches each 16 KiB chunk of the stream ONCE by LDS-DMA into a 4-slot ring and
-// its four waves read it with ds_read_b128.  Two things that each cost more than they look:
-//   * a vector-memory instruction whose address is a 64-bit VGPR pair per lane holds up the issuing
-//     SIMD's matrix pipe for ~40 cycles on gfx950, whatever it moves (4 active lanes cost the same as
-//     64): the DMA uses the SGPR-base + 32-bit-lane-offset form (158 -> 150 ms);
+// 232 ms); the workgroup fetches each 16 KiB chunk of the stream ONCE through the LDS-DMA ring of
+// weight_ring.h and its four waves read it with ds_read_b128.  Two things that each cost more than they look:
+//   * the form of the DMA's source address (weight_ring.h): SGPR base + 32-bit lane offset instead of a
+//     64-bit VGPR pair per lane was 158 -> 150 ms here;
 //   * the six hidden layers share one unrolled body so that the hot code of the 4 workgroups that share
 //     an instruction cache stays small.
 // Measured on MI355X, 23.5 M samples: 150 ms = 144.8 TFLOP/s = 92 % of the 157.3 TFLOP/s fp32-MFMA peak
@@ -23,11 +22,11 @@
 // block is W[out = 16*ob' + i][16*G + 4*g .. +3] -- a contiguous float4 of the torch weight row.
 // Packed as [G][ob'][lane] float4: one group G of a 16-block layer is exactly one 16 KiB chunk.
 #include "common.h"
+#include "mfma16.h"
+#include "weight_ring.h"
 
 namespace occ {
 namespace m16 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWidth = 256;
 constexpr int kOB = kWidth / 16;          // 16 output blocks of 16 features
@@ -36,7 +35,6 @@ constexpr int kKS_X = 17;                 // k-steps of the 68-wide sample row: 
 constexpr int kKS_Hidden = kWidth / 4;    // 64
 constexpr int kKS_L0Rgb = 16 + kKS_X;     // 64 geometry features + the sample row
 
-constexpr int groups_of(int ks) { return (ks + 3) / 4; }
 enum LayerKind { kL0Geo = 0, kHidden = 1, kGeoHead = 2, kL0Rgb = 3 };
 
 // position in the 68-wide sample row [agg35, var, enc32] carried by x k-step t in lane group g
@@ -94,20 +92,19 @@ __global__ void pack_rows_kernel(const float *__restrict__ W, const float *__res
 
 // ---------------------------------------------------------------------------------------
 // Weight stream: 16 KiB chunks (one group of 4 k-steps x 16 output blocks x 64 lanes x float4; the
-// 4-block geometry head packs 4 groups per chunk), fetched ONCE per workgroup by LDS-DMA into a
-// 4-slot ring and read by all four waves with ds_read_b128.  Two workgroups (2 x 4 waves) are
-// resident per CU; they drift apart, so one's barriers and epilogues sit under the other's MFMAs.
+// 4-block geometry head packs 4 groups per chunk) through the ring of weight_ring.h.  Two workgroups
+// (2 x 4 waves) are resident per CU; they drift apart, so one's barriers and epilogues sit under the
+// other's MFMAs.
 // ---------------------------------------------------------------------------------------
 constexpr int kWaves = 4;                            // waves per workgroup, 16 samples each
-constexpr int kFrags = 16 / kWaves;                  // 1 KiB fragments of a chunk issued by each wave
-constexpr int kRingSlots = 4;
 constexpr int kChunkF4 = 1024;                       // float4 units per chunk
+typedef WeightRing<kChunkF4, kChunkF4 / 64 / kWaves> Ring;      // 4 pieces of 1 KiB per wave and chunk
 constexpr int kC_L0Geo = groups_of(kKS_X);           // 5
 constexpr int kC_Hidden = groups_of(kKS_Hidden);     // 16
 constexpr int kC_GeoHead = kC_Hidden / 4;            // 4
 constexpr int kC_L0Rgb = groups_of(kKS_L0Rgb);       // 9
 constexpr int kChunksTotal = kC_L0Geo + 3 * kC_Hidden + kC_GeoHead + kC_L0Rgb + 3 * kC_Hidden;
-constexpr int kTailChunks = kRingSlots;              // zero chunks the prefetch runs into
+constexpr int kTailChunks = Ring::kTailChunks;       // (the kernel enters a chunk ahead of the one it multiplies)
 
 struct Aux {       // fp32 side data (floats): biases and dot rows in torch order
     static constexpr int kGeoL0B = 0;
@@ -133,38 +130,6 @@ struct Stream {    // packed blob: [chunk stream][tail zeros][aux], offsets in f
 };
 static_assert(Stream::kTail == (int64_t)kChunksTotal * Stream::kChunkFloats, "chunk stream is contiguous");
 
-template <int OB>
-__device__ __forceinline__ void lds_bias(f32x4 (&acc)[OB], const float *aux, int g) {
-    const f32x4 *B4 = reinterpret_cast<const f32x4 *>(aux);
-#pragma unroll
-    for (int ob = 0; ob < OB; ob++) acc[ob] = B4[ob * 4 + g];
-}
-
-__device__ __forceinline__ void relu_into(f32x4 (&act)[kOB], const f32x4 (&acc)[kOB]) {
-#pragma unroll
-    for (int ob = 0; ob < kOB; ob++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) act[ob][r] = relu_arith(acc[ob][r]);
-    }
-}
-
-// dot product of a torch-layout weight row (in LDS) with the lane's 64 activations (features
-// 16*ob+4*g+r); the other three quarters live in the lanes s+16, s+32, s+48
-__device__ __forceinline__ float dot_row(const f32x4 (&act)[kOB], const float *Wrow, int g) {
-    const f32x4 *W4 = reinterpret_cast<const f32x4 *>(Wrow);
-    float s = 0.0f;
-#pragma unroll
-    for (int ob = 0; ob < kOB; ob++) {
-        const f32x4 w = W4[ob * 4 + g];
-#pragma unroll
-        for (int r = 0; r < 4; r++) s = __fmaf_rn(w[r], act[ob][r], s);
-    }
-    s += __shfl_xor(s, 16);
-    return s + __shfl_xor(s, 32);
-}
-
-static_assert(kFrags == 4, "OCC16_ENTER waits with vmcnt(8) = 2 chunks x 4 DMAs per wave");
-
 // n_dev (nullable): the number of rows actually present, in device memory (the live-sample count of the
 // frame, written by occnerf_live_rows on the same stream); the launch is sized for N_max rows and the
 // workgroups beyond *n_dev leave at once -- no host round trip to learn the count.
@@ -177,10 +142,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void canonical_mlp_lds_kernel(const
                                                                            float *__restrict__ raw) {
     const int64_t N = n_dev ? (int64_t)*n_dev : N_max;
     if ((int64_t)blockIdx.x * (16 * kWaves) >= N) return;          // uniform for the workgroup
-    // ONE __shared__ object (a second one makes hipcc drain vmcnt before every ds_read)
-    __shared__ __attribute__((aligned(16))) f32x4 smem[kRingSlots * kChunkF4 + Aux::kTotal / 4];
-    f32x4 *ring = smem;
-    float *aux = reinterpret_cast<float *>(smem + kRingSlots * kChunkF4);
+    __shared__ __attribute__((aligned(16))) f32x4 smem[Ring::kLdsUnits + Aux::kTotal / 4];      // [ring | aux]
+    float *aux = reinterpret_cast<float *>(smem + Ring::kLdsUnits);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -205,38 +168,20 @@ __global__ __launch_bounds__(kWaves * 64, 2) void canonical_mlp_lds_kernel(const
     }
     __syncthreads();
 
-    // ---- weight stream: chunk c lives in ring slot c & 3 ----
-    const f32x4 *stream = reinterpret_cast<const f32x4 *>(pk);
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) f32x4 *)ring;
-    // LDS-DMA, wave-uniform source base (SGPR pair) + 32-bit lane offset (see the header comment)
-    auto issue1 = [&](int c, int f) {      // 1 KiB fragment f of this wave's share of chunk c
-        const int frag = wave * kFrags + f;
-        unsigned keep;      // M0 carries the wave-uniform LDS destination; lane i lands at +16 i
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(lane * 16), "s"(stream + (size_t)c * kChunkF4 + frag * 64),
-                       "s"(ring_lds + (unsigned)(((c & (kRingSlots - 1)) * kChunkF4 + frag * 64) * 16))
-                     : "memory");
-    };
-    auto issue = [&](int c) {
-#pragma unroll
-        for (int f = 0; f < kFrags; f++) issue1(c, f);
-    };
+    // ---- weight stream (weight_ring.h): chunk c lives in ring slot c & 3 ----
+    const Ring ring(reinterpret_cast<const f32x4 *>(pk), smem, wave, lane);
     int c = 0;                     // next chunk to enter
-    issue(0);
-    issue(1);
-    issue(2);
+    ring.chunk(0, 0);
+    ring.chunk(1, 1);
+    ring.chunk(2, 2);
 
-    // Enter chunk c: wait for it (own quarter landed: 3 chunks x kFrags DMAs are outstanding, vmcnt(2*kFrags)
-    // retires the oldest; the two younger chunks stay in flight), rendezvous, point slot_ at it.  After the
-    // barrier every wave has finished reading chunk c-1 (its ds_reads completed before the lgkmcnt(0)), so
-    // the step that follows may refill that slot.
+    // Enter chunk c and point slot_ at it; the step that follows refills the slot of chunk c-1 (this wave's
+    // ds_reads of it completed before the wait's lgkmcnt(0)).
     const f32x4 *slot_;
 #define OCC16_ENTER()                                                  \
-    asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");        \
+    Ring::wait_oldest_and_lds();                                       \
     __builtin_amdgcn_s_barrier();                                      \
-    slot_ = ring + (c & (kRingSlots - 1)) * kChunkF4;                  \
+    slot_ = ring.slot<f32x4>(c);                                              \
     c++;
 #define OCC16_READ_HALF(W, HALF)                                       \
     _Pragma("unroll") for (int ob_ = 0; ob_ < 8; ob_++) W[ob_] = slot_[((HALF) * 8 + ob_) * 64 + lane];
@@ -246,13 +191,13 @@ __global__ __launch_bounds__(kWaves * 64, 2) void canonical_mlp_lds_kernel(const
     // first, enters the next chunk, reads ITS first half, computes the second.
     f32x4 wA[8];
     OCC16_ENTER()
-    issue(3);
+    ring.chunk(3, 3);
     OCC16_READ_HALF(wA, 0)
 
     // one chunk (= one group of 4 k-steps) of a 16-block layer
     // (the refill DMA of the chunk entered before a second half -- chunk c+2 after the c++ -- is issued
     // from inside that half)
-#define OCC16_DMA(RR) issue1(c + 2, RR);
+#define OCC16_DMA(RR) ring.piece(c + 2, c + 2, RR);
 #define OCC16_HALF(W, HH, CL, KS, ACC, BOP)                                                      \
     _Pragma("unroll") for (int rr_ = 0; rr_ < 4; rr_++) {                                        \
         const int t_ = (CL) * 4 + rr_;                                                           \
@@ -321,7 +266,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void canonical_mlp_lds_kernel(const
         OCC16_LAYER(kC_Hidden, kKS_Hidden, acc, BOP_ACT)
         relu_into(act, acc);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the tail chunks: nobody computes with them
+    Ring::drain();      // the tail chunks: nobody computes with them
     float rgb[3];
 #pragma unroll
     for (int ch = 0; ch < 3; ch++) rgb[ch] = dot_row(act, aux + Aux::kOut + ch * kWidth, g) + aux[Aux::kOut + 3 * kWidth + ch];

@@ -1,6 +1,6 @@
 // Layout of the canonical MLP's packed operands, shared by the renderer's kernels (mlp.hip) and the training step's fused
 // trunk forward (trunks.hip): the register <-> feature map of the transposed 32x32 MFMA scheme, the fp32 blob of biases and
-// head rows, the k-step counts of the 16-wide (2-byte operand) kernels and the LDS-DMA helper.
+// head rows and the k-step counts of the 16-wide (2-byte operand) kernels.
 #pragma once
 
 #include "common.h"
@@ -8,7 +8,6 @@
 namespace occ {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kWidth = 256;
 constexpr int kOB = kWidth / 32;     // 8 output blocks of 32 features
@@ -73,17 +72,5 @@ __host__ __device__ inline int out_row(int kind, int row, int out_dim) {
 constexpr int kS_L0Geo = 5;                 // ceil(34 / 8) k-steps of 16 (8 per half-wave)
 constexpr int kS_Hidden = kWidth / 16;      // 16
 constexpr int kS_L0Rgb = 4 + 5;             // 64 geometry features + 34 x-slots
-
-// LDS-DMA of 64 x 16 B: wave-uniform source base (SGPR pair) + 32-bit lane offset ("saddr" form -- a
-// 64-bit VGPR address per lane costs the issuing SIMD ~40 cycles of matrix-pipe time per instruction on
-// gfx950), wave-uniform LDS destination in M0 (lane i lands at +16 i).
-__device__ __forceinline__ void glds16(const void *gbase, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(lane_off), "s"(gbase), "s"(lds_dst)
-                 : "memory");
-}
 
 }  // namespace occ

@@ -17,11 +17,11 @@
 // MFMA per wave: 80 + 3*256 + 336 + 256 = 1440 (algorithmic 1424).  Bound: fp32 MFMA.
 #include "common.h"
 #include "split.h"
+#include "weight_ring.h"
 
 namespace occ {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kNrW = 128, kNrOB = 4;
 constexpr int kCond = 69, kEmb = 36, kEmbHalf = 18;
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void nonrigid_kernel(const float *xyz_in /*
 
 // =======================================================================================
 // bf16x3 variant (see mlp.hip): hi/lo bf16 operands, Wh*xh + Wh*xl + Wl*xh, fp32 accumulate,
-// weights streamed once per workgroup through an LDS ring by LDS-DMA.  A 16 KiB chunk holds two
+// weights streamed once per workgroup through the LDS-DMA ring of weight_ring.h.  A 16 KiB chunk holds two
 // 16-wide k-steps x {hi,lo} x 4 output blocks; 23 chunks per tile.
 // =======================================================================================
 constexpr int kNrS_E = 3;                       // embedding: 18 slots per half -> 3 k-steps (6 pad)
@@ -239,7 +239,7 @@ constexpr int kNrSteps = kNrS_E + 3 * kNrS_H + (kNrS_H + kNrS_E) + kNrS_H;   // 
 static_assert(kNrSteps % 2 == 0, "two k-steps per chunk");
 constexpr int kNrChunks = kNrSteps / 2;
 constexpr int kNrChunkUnits = 1024;             // 16-byte units per chunk
-constexpr int kNrRing = 4;
+typedef WeightRing<kNrChunkUnits, kNrChunkUnits / 64 / 4> NrRing;      // 4 pieces of 1 KiB per wave and chunk
 constexpr int kNrStepUnits = 2 * kNrOB * 64;    // [hi|lo][ob][lane]
 
 struct NrAux {      // floats in LDS
@@ -275,18 +275,6 @@ __device__ __forceinline__ NrSplitT<P> nr_split8(const float (&v)[8]) {
     return o;
 }
 
-// LDS-DMA of 64 x 16 B: wave-uniform source base (SGPR pair) + 32-bit lane offset ("saddr" form -- a
-// 64-bit VGPR address per lane costs the issuing SIMD ~40 cycles of matrix-pipe time per instruction on
-// gfx950), wave-uniform LDS destination in M0 (lane i lands at +16 i).
-__device__ __forceinline__ void nr_glds16(const void *gbase, unsigned lane_off, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(lane_off), "s"(gbase), "s"(lds_dst)
-                 : "memory");
-}
-
 template <typename P, bool WATCH /* track the ReLU outputs and report leaving the policy's domain (split.h) */>
 __global__ __launch_bounds__(256, 2) void nonrigid_split_kernel(const float *xyz_in /* may alias xyz_out (in-place): no __restrict__ */, int64_t N_max,
                                                                  const int32_t *__restrict__ rows /*nullable: sample of entry n*/,
@@ -298,9 +286,8 @@ __global__ __launch_bounds__(256, 2) void nonrigid_split_kernel(const float *xyz
     typedef NrSplitT<P> NrSplit;
     float amax = 0.0f;      // P::kBounded policies: running packed-half maximum of the ReLU outputs' hi pieces (split.h)
     constexpr float kSx = P::kSx, kInvSx = 1.0f / P::kSx;
-    __shared__ __attribute__((aligned(16))) V8 smem[kNrRing * kNrChunkUnits + NrAux::kTotal / 4];
-    V8 *ring = smem;
-    float *aux = reinterpret_cast<float *>(smem + kNrRing * kNrChunkUnits);
+    __shared__ __attribute__((aligned(16))) V8 smem[NrRing::kLdsUnits + NrAux::kTotal / 4];      // [ring | aux]
+    float *aux = reinterpret_cast<float *>(smem + NrRing::kLdsUnits);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 31, h = lane >> 5;
@@ -349,29 +336,21 @@ __global__ __launch_bounds__(256, 2) void nonrigid_split_kernel(const float *xyz
     }
     __syncthreads();
 
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) V8 *)ring;
-    auto issue = [&](int g) {
-#pragma unroll
-        for (int f = 0; f < 4; f++) {
-            const int frag = wave * 4 + f;
-            nr_glds16(pkh + (size_t)g * kNrChunkUnits + frag * 64, lane * 16,
-                      ring_lds + (unsigned)(((g & (kNrRing - 1)) * kNrChunkUnits + frag * 64) * 16));
-        }
-    };
-    issue(0);
-    issue(1);
-    issue(2);
+    const NrRing ring(pkh, smem, wave, lane);
+    ring.chunk(0, 0);
+    ring.chunk(1, 1);
+    ring.chunk(2, 2);
 
     // The k-steps of the whole network form one stream: step index `st` (compile-time after
     // unrolling) -> chunk st/2, half st%2.  Entering a new chunk = counted wait + barrier + refill.
-    const V8 *slot = ring;
+    const V8 *slot = smem;
 #define NR_STEP(ST, ACC, BSPLIT)                                                                   \
     {                                                                                              \
         if (((ST) & 1) == 0) {                                                                     \
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                                       \
+            NrRing::wait_oldest();                                                                 \
             __builtin_amdgcn_s_barrier();                                                          \
-            issue((ST) / 2 + 3);                                                                   \
-            slot = ring + (((ST) / 2) & (kNrRing - 1)) * kNrChunkUnits;                            \
+            ring.chunk((ST) / 2 + 3, (ST) / 2 + 3);                                                \
+            slot = ring.slot<V8>((ST) / 2);                                                        \
         }                                                                                          \
         const V8 *st_ = slot + ((ST) & 1) * kNrStepUnits;                                          \
         V8 ah_[kNrOB], al_[kNrOB];                                                                 \
@@ -429,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void nonrigid_split_kernel(const float *xyz
     NR_BIAS(NrAux::kL5B)
 #pragma unroll
     for (int s = 0; s < kNrS_H; s++) NR_STEP(2 * kNrS_E + 4 * kNrS_H + s, acc, bact[s])
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    NrRing::drain();
 
     float off[3];
 #pragma unroll
@@ -485,7 +464,7 @@ OCC_API int occnerf_nonrigid_pack(const float *const *h_W, const float *const *h
 }
 
 OCC_API int64_t occnerf_nonrigid_packed_bf16_bytes(void) {
-    return ((int64_t)occ::kNrChunks + occ::kNrRing - 1) * occ::kNrChunkUnits * 16;     // + read-ahead tail
+    return ((int64_t)occ::kNrChunks + occ::NrRing::kAhead) * occ::kNrChunkUnits * 16;     // + read-ahead tail
 }
 
 template <typename P>

@@ -7,9 +7,8 @@
 // A wave carries TWO tiles of 16 samples (2 x (32 + 32) registers of activations + accumulators) and every
 // weight register feeds one MFMA of each tile, so LDS reads and DMA per sample are half of what one tile
 // per wave would need; 2 waves per SIMD.  The weight stream (46 chunks of 8 KiB = one group of 4 k-steps x
-// 8 output blocks) goes through a 4-slot LDS ring exactly as in mlp16.hip (LDS-DMA with SGPR base + 32-bit
-// lane offset, one raw barrier + counted vmcnt per chunk, weight registers pipelined across chunks and
-// layers).  The 69 condition inputs are the same for every sample of a frame: their share of layer 0 is
+// 8 output blocks) goes through the LDS-DMA ring of weight_ring.h, scheduled as in mlp16.hip (weight
+// registers pipelined across chunks and layers).  The 69 condition inputs are the same for every sample of a frame: their share of layer 0 is
 // folded into its bias once per call (bias first, then k = 0..68 -- the order a dense evaluation uses).
 //
 // Embedding k order (free to choose, the weights are packed to match): k-steps 2m, 2m+1 (m < 4) carry
@@ -17,23 +16,23 @@
 // (g&1); angle A = (octave A/3, axis A%3), torch feature index octave*6 + cos*3 + axis.  So a lane
 // evaluates 5 sin + 5 cos per sample.
 #include "common.h"
+#include "mfma16.h"
+#include "weight_ring.h"
 
 namespace occ {
 namespace nr16 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kW = 128, kOB = kW / 16;            // 8 output blocks of 16 features
 constexpr int kCond = 69, kEmb = 36;
 constexpr int kKS_E = 9, kKS_H = kW / 4, kKS_Skip = kKS_H + kKS_E;
-constexpr int groups_of(int ks) { return (ks + 3) / 4; }
 constexpr int kC_E = groups_of(kKS_E);            // 3
 constexpr int kC_H = groups_of(kKS_H);            // 8
 constexpr int kC_Skip = groups_of(kKS_Skip);      // 11 (8 activation groups + 3 embedding groups)
 constexpr int kChunks = kC_E + 3 * kC_H + kC_Skip + kC_H;      // 46
-constexpr int kWaves = 4, kFrags = 2;             // 8 KiB chunk = 8 fragments of 1 KiB, 2 per wave
-constexpr int kRingSlots = 4, kTailChunks = kRingSlots;
+constexpr int kWaves = 4;
 constexpr int kChunkF4 = 512;
+typedef WeightRing<kChunkF4, kChunkF4 / 64 / kWaves> Ring;      // 8 KiB chunk = 8 pieces of 1 KiB, 2 per wave
+constexpr int kTailChunks = Ring::kTailChunks;    // (part of the blob's layout; the stream wraps before it reaches them)
 
 enum Kind { kL0 = 0, kHidden = 1, kSkip = 2 };
 
@@ -124,10 +123,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
     const int64_t N = n_dev ? (int64_t)*n_dev : N_max;
     const int64_t ntiles = (N + 32 * kWaves - 1) / (32 * kWaves);   // a workgroup's tile: 4 waves x 32 samples
     if ((int64_t)blockIdx.x >= ntiles) return;                      // uniform for the workgroup
-    // ONE __shared__ object (a second one makes hipcc drain vmcnt before every ds_read)
-    __shared__ __attribute__((aligned(16))) f32x4 smem[kRingSlots * kChunkF4 + Aux::kTotal / 4];
-    f32x4 *ring = smem;
-    float *aux = reinterpret_cast<float *>(smem + kRingSlots * kChunkF4);
+    __shared__ __attribute__((aligned(16))) f32x4 smem[Ring::kLdsUnits + Aux::kTotal / 4];      // [ring | aux]
+    float *aux = reinterpret_cast<float *>(smem + Ring::kLdsUnits);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -139,42 +136,26 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
     // The workgroup is PERSISTENT: it walks tiles blockIdx.x, blockIdx.x + gridDim.x, ... and the ring keeps running
     // across them (the chunks of the next tile's first layer are requested during this tile's last), so a tile pays neither
     // a workgroup launch nor the first chunk's DMA latency -- 8-10 % of a 128-sample workgroup's 38 us before.
-    const f32x4 *stream = reinterpret_cast<const f32x4 *>(pk);
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) f32x4 *)ring;
-    auto issue1 = [&](int c, int cs, int f) {      // 1 KiB fragment f of this wave's share of stream chunk cs -> slot of c
-        const int frag = wave * kFrags + f;
-        unsigned keep;      // M0 carries the wave-uniform LDS destination; lane i lands at +16 i
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(keep)
-                     : "v"(lane * 16), "s"(stream + (size_t)cs * kChunkF4 + frag * 64),
-                       "s"(ring_lds + (unsigned)(((c & (kRingSlots - 1)) * kChunkF4 + frag * 64) * 16))
-                     : "memory");
-    };
-    auto issue = [&](int c, int cs) {
-#pragma unroll
-        for (int f = 0; f < kFrags; f++) issue1(c, cs, f);
-    };
+    const Ring ring(reinterpret_cast<const f32x4 *>(pk), smem, wave, lane);
     int c = 0;                     // chunks entered so far (ring position)
     int ci = 4;                    // stream chunk the next refill brings (always the (c + 2)-th to enter)
-    issue(0, 0);
-    issue(1, 1);
-    issue(2, 2);
+    ring.chunk(0, 0);
+    ring.chunk(1, 1);
+    ring.chunk(2, 2);
 
-    // Enter the next chunk (3 chunks x kFrags DMAs outstanding; vmcnt(2*kFrags) retires the oldest), rendezvous; after
-    // the barrier every wave has finished reading the previous chunk, whose slot the following step refills.
+    // Enter the next chunk (weight_ring.h); the step that follows refills the previous chunk's slot.
     const f32x4 *slot_;
 #define NR16_ENTER()                                                   \
-    asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");        \
+    Ring::wait_oldest_and_lds();                                       \
     __builtin_amdgcn_s_barrier();                                      \
-    slot_ = ring + (c & (kRingSlots - 1)) * kChunkF4;                  \
+    slot_ = ring.slot<f32x4>(c);                                              \
     c++;
 #define NR16_READ_HALF(W, HALF)                                        \
     _Pragma("unroll") for (int ob_ = 0; ob_ < 4; ob_++) W[ob_] = slot_[((HALF) * 4 + ob_) * 64 + lane];
 
     f32x4 wA[4];
     NR16_ENTER()                   // (its lgkmcnt(0) + barrier also publish aux)
-    issue(3, 3);
+    ring.chunk(3, 3);
     NR16_READ_HALF(wA, 0)
 
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -218,9 +199,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
 #define NR16_HALF(W, HH, CL, KS, BOP)                                                            \
     _Pragma("unroll") for (int rr_ = 0; rr_ < 4; rr_++) {                                        \
         const int t_ = (CL) * 4 + rr_;                                                           \
-        if ((HH) == 1 && rr_ < kFrags) {                                                         \
-            issue1(c + 2, ci, rr_);                                                              \
-            if (rr_ == kFrags - 1) ci = ci + 1 == kChunks ? 0 : ci + 1;                          \
+        if ((HH) == 1 && rr_ < Ring::kPieces) {                                                  \
+            ring.piece(c + 2, ci, rr_);                                                          \
+            if (rr_ == Ring::kPieces - 1) ci = ci + 1 == kChunks ? 0 : ci + 1;                   \
         }                                                                                        \
         if (t_ < (KS)) {                                                                         \
             _Pragma("unroll") for (int ob_ = 0; ob_ < 4; ob_++) {                                \
@@ -239,17 +220,11 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
         NR16_HALF(wB_, 1, c_, KS, BOP)                                                           \
     }
 #define NR16_BIAS(OFF)                                                                           \
-    _Pragma("unroll") for (int ob_ = 0; ob_ < kOB; ob_++) {                                      \
-        const f32x4 b_ = reinterpret_cast<const f32x4 *>(aux + (OFF))[ob_ * 4 + g];              \
-        acc[0][ob_] = b_;                                                                        \
-        acc[1][ob_] = b_;                                                                        \
-    }
+    lds_bias<kOB>(acc[0], aux + (OFF), g);                                                       \
+    _Pragma("unroll") for (int ob_ = 0; ob_ < kOB; ob_++) acc[1][ob_] = acc[0][ob_];
 #define NR16_RELU()                                                                              \
-    _Pragma("unroll") for (int T_ = 0; T_ < 2; T_++) {                                           \
-        _Pragma("unroll") for (int ob_ = 0; ob_ < kOB; ob_++) {                                  \
-            _Pragma("unroll") for (int r_ = 0; r_ < 4; r_++) act[T_][ob_][r_] = relu_arith(acc[T_][ob_][r_]); \
-        }                                                                                        \
-    }
+    relu_into<kOB>(act[0], acc[0]);                                                              \
+    relu_into<kOB>(act[1], acc[1]);
 
     f32x4 acc[2][kOB], act[2][kOB];
 #define BOP_E(T, t) e[T][t]
@@ -276,18 +251,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
     for (int T = 0; T < 2; T++) {
         float off[3];
 #pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-            const f32x4 *W4 = reinterpret_cast<const f32x4 *>(aux + Aux::kOutW + ch * kW);
-            float sum = 0.0f;
-#pragma unroll
-            for (int ob = 0; ob < kOB; ob++) {
-                const f32x4 w = W4[ob * 4 + g];
-#pragma unroll
-                for (int r = 0; r < 4; r++) sum = __fmaf_rn(w[r], act[T][ob][r], sum);
-            }
-            sum += __shfl_xor(sum, 16);
-            off[ch] = sum + __shfl_xor(sum, 32) + aux[Aux::kOutB + ch];
-        }
+        for (int ch = 0; ch < 3; ch++) off[ch] = dot_row<kOB>(act[T], aux + Aux::kOutW + ch * kW, g) + aux[Aux::kOutB + ch];
         const int64_t n = base + T * 16 + s;
         if (g == 0 && n < N) {
             const int64_t nd = r_cur[T];
@@ -296,7 +260,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nonrigid_lds_kernel(const floa
         }
     }
     }       // tiles
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // chunks still in flight: nobody computes with them
+    Ring::drain();      // chunks still in flight: nobody computes with them
 #undef BOP_E
 #undef BOP_A
 #undef BOP_SKIP

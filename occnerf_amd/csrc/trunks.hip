@@ -13,8 +13,8 @@
 //   * one wave = 32 samples; a layer is computed transposed, D'[feature][sample] = W x act, so its accumulators -- after bias,
 //     ReLU and the rounding to bf16 that the staged forward applied when it stored them -- ARE the next layer's B operands
 //     (mlp_layout.h: register <-> feature map); same rounding points as the staged forward, different summation order.
-//   * weights: 2-byte stream [k-step][output block][lane] x 16 B, fetched once per 4-wave workgroup by LDS-DMA into a 4-slot
-//     ring of 16 KiB chunks (two 16-wide k-steps of 8 output blocks), counted vmcnt + one raw s_barrier per chunk (mlp.hip).
+//   * weights: 2-byte stream [k-step][output block][lane] x 16 B, fetched once per 4-wave workgroup through the LDS-DMA ring
+//     of weight_ring.h in 16 KiB chunks (two 16-wide k-steps of 8 output blocks).
 //   * saved activations leave through LDS: a wave writes its 32 x 128 tile in the accumulator layout (8 B per lane), reads it
 //     back row by row and stores 16 B per lane -- 4 rows x 256 contiguous bytes per instruction (linear.hip measured what the
 //     direct 8-byte scatter costs).  Stores and LDS-DMA share vmcnt and complete out of order with respect to each other:
@@ -29,6 +29,7 @@
 // only more samples per workgroup (64 per wave: twice the accumulators) would amortise it further.
 #include "common.h"
 #include "mlp_layout.h"
+#include "weight_ring.h"
 
 namespace occ {
 namespace trunks {
@@ -38,11 +39,11 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kRing = 4;                                                   // chunks resident / in flight (see OCC_ENTER)
 constexpr int kChunkUnits = 1024;                                          // 16-byte units per chunk: 2 k-steps x 8 blocks x 64 lanes
+typedef WeightRing<kChunkUnits, kChunkUnits / 64 / 4> Ring;                // a wave fetches 4 of a chunk's 16 pieces
 constexpr int kT_L0Geo = (kS_L0Geo + 1) / 2 * 2, kT_L0Rgb = (kS_L0Rgb + 1) / 2 * 2;      // k-steps padded to whole chunks: 6, 10
 constexpr int kChunks = kT_L0Geo / 2 + 3 * kS_Hidden / 2 + kS_Hidden / 8 + kT_L0Rgb / 2 + 3 * kS_Hidden / 2;      // 58
-constexpr int kTailChunks = kRing;                                         // zero chunks the prefetch may touch (one chunk is read ahead)
+constexpr int kTailChunks = Ring::kTailChunks;                             // (one chunk is read ahead)
 constexpr int kStagePitch = 272;                                           // bytes per staged row: 128 features + 16 B pad
 constexpr int kStageBytes = 32 * kStagePitch;                              // per wave
 
@@ -104,13 +105,11 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
 }
 
 __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a) {
-    // ONE __shared__ object (a second one makes hipcc drain vmcnt before every ds_read): [ring | stage x 4 waves | aux]
-    __shared__ __attribute__((aligned(16))) bf16x8 smem[kRing * kChunkUnits + 4 * kStageBytes / 16 + Aux::kTotal / 4];
-    bf16x8 *ring = smem;
+    __shared__ __attribute__((aligned(16))) bf16x8 smem[Ring::kLdsUnits + 4 * kStageBytes / 16 + Aux::kTotal / 4];      // [ring | stage x 4 waves | aux]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    char *stage = reinterpret_cast<char *>(smem + kRing * kChunkUnits) + wave * kStageBytes;
-    float *aux = reinterpret_cast<float *>(smem + kRing * kChunkUnits + 4 * kStageBytes / 16);
+    char *stage = reinterpret_cast<char *>(smem + Ring::kLdsUnits) + wave * kStageBytes;
+    float *aux = reinterpret_cast<float *>(smem + Ring::kLdsUnits + 4 * kStageBytes / 16);
     const int j = lane & 31, h = lane >> 5;
     const int64_t m0 = ((int64_t)blockIdx.x * 4 + wave) * 32;            // first row of this wave's tile
     const int64_t n = m0 + j;
@@ -159,23 +158,15 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the input loads and the X0 stores, before any DMA is counted
     __syncthreads();
 
-    // ---- weight stream: chunk g lives in ring slot g & 3; a wave fetches 2 of a chunk's 8 KiB ----
-    const unsigned ring_lds = (unsigned)(size_t)(__attribute__((address_space(3))) bf16x8 *)ring;
-    auto issue_piece = [&](int g, int f) {
-        const int frag = wave * 4 + f;
-        glds16(a.pkh + (size_t)g * kChunkUnits + frag * 64, lane * 16,
-               ring_lds + (unsigned)(((g & (kRing - 1)) * kChunkUnits + frag * 64) * 16));
-    };
+    // ---- weight stream (weight_ring.h): chunk g lives in ring slot g & 3 ----
+    const Ring ring(a.pkh, smem, wave, lane);
     int g = 0;                     // next chunk to consume
 #pragma unroll
-    for (int c = 0; c < kRing; c++) {      // (one chunk is read ahead into registers: its slot refills a chunk later)
-#pragma unroll
-        for (int f = 0; f < 4; f++) issue_piece(c, f);
-    }
-    // Stores and LDS-DMA share vmcnt and retire out of order with respect to each other, so a counted wait is only meaningful
-    // while DMAs alone are in flight.  A store phase therefore BEGINS with vmcnt(0) -- the 3 chunks ahead are in LDS (they were
-    // issued 2-6 k-steps ago) -- and the next 3 chunk entries need no wait at all; by the 4th, whose DMA was issued after the
-    // stores, 6 k-steps (~3 K cycles) have passed and the stores have retired: the counted wait resumes without a stall.
+    for (int c = 0; c < Ring::kSlots; c++) ring.chunk(c, c);      // (one chunk is read ahead into registers: its slot refills a chunk later)
+    // The ring's counted wait is only meaningful while DMAs alone are in flight, and this kernel stores in mid-stream.  A
+    // store phase therefore BEGINS with vmcnt(0) -- the 3 chunks ahead are in LDS (they were issued 2-6 k-steps ago) -- and the
+    // next 3 chunk entries need no wait at all; by the 4th, whose DMA was issued after the stores, 6 k-steps (~3 K cycles)
+    // have passed and the stores have retired: the counted wait resumes without a stall.
     int landed = 0;                // chunks ahead known to be in LDS (set by a store phase)
 
     // enter chunk g (to READ it ahead, while chunk g - 1 is multiplied): this wave's pieces of it have landed, rendezvous --
@@ -184,18 +175,18 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
     if (landed > 0) {                                                                  \
         landed--;                                                                      \
     } else {                                                                           \
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");                               \
+        Ring::wait_oldest();                                                           \
     }                                                                                  \
     __builtin_amdgcn_s_barrier();                                                      \
-    const bf16x8 *slot_ = ring + (g & (kRing - 1)) * kChunkUnits;                      \
+    const bf16x8 *slot_ = ring.slot<bf16x8>(g);                                        \
     g++;
-#define OCC_REFILL(F)                                   \
-    __builtin_amdgcn_sched_barrier(0);                  \
-    issue_piece(g + (kRing - 2), F);                    \
+#define OCC_REFILL(F)                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                 \
+    ring.piece(g + Ring::kAhead - 1, g + Ring::kAhead - 1, F);         \
     __builtin_amdgcn_sched_barrier(0);
-#define OCC_STORE_PHASE()                               \
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    \
-    landed = kRing - 1;
+#define OCC_STORE_PHASE()                                              \
+    Ring::drain();                                                     \
+    landed = Ring::kAhead;
 #define OCC_MMA(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_bf16((A_), (B_), (C_), 0, 0, 0)
 
     // Two 16-wide k-steps per chunk, 8 output blocks.  The 16 operand fragments of the NEXT chunk are read while the current
@@ -406,7 +397,7 @@ __global__ __launch_bounds__(256, 1) void trunks_forward_kernel(const FwdArgs a)
         rgb[c] = (sacc + __shfl_xor(sacc, 32)) + aux[Aux::kOut + 3 * kWidth + c];
     }
     if (h == 0 && n < a.M) *reinterpret_cast<f32x4 *>(a.raw4 + n * 4) = f32x4{rgb[0], rgb[1], rgb[2], sigma};
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the 3 tail chunks: nobody reads them
+    Ring::drain();      // the 3 tail chunks: nobody reads them
 #undef BOPS_X
 #undef BOPS_ACT
 #undef BOPS_RGB0

@@ -1,4 +1,5 @@
-"""CPU: what the compiler makes of the two fp32 LDS-staged MLP kernels (mlp16.hip, nonrigid16.hip).
+"""CPU: what the compiler makes of the streamed MLP kernels -- the two fp32 LDS-staged ones (mlp16.hip, nonrigid16.hip), the
+split-operand kernels (mlp.hip, nonrigid.hip) and the fused trunk forward (trunks.hip), all on the ring of weight_ring.h.
 
 Beside an fp32 MFMA nothing else issues on a gfx950 SIMD, so the kernels' budget of other instructions and their
 register / LDS footprint (two waves per SIMD, two workgroups per CU) are part of what they are.  Each source is
@@ -40,18 +41,25 @@ def _compile(src, outdir):
     return open(out).read()
 
 
-def _kernel(text, fragment):
-    """-> (body: the instruction lines of the kernel whose mangled name contains `fragment`, meta: its metadata as a dict)."""
-    m = re.search(r'^(\w*%s\w*):' % fragment, text, re.M)
-    assert m, fragment
-    sym = m.group(1)
-    body = text[m.end():]
-    body = body[:body.index('s_endpgm')]
+def _kernels(text, fragment):
+    """-> [(symbol, body: the instruction lines, meta: the metadata as a dict)] of the kernels whose mangled name contains `fragment`."""
     notes = text[text.index('amdhsa.kernels:'):]
     blocks = re.split(r'^  - (?=\.)', notes, flags=re.M)
-    mine = [b for b in blocks if re.search(r'^\s*\.name:\s+%s\s*$' % re.escape(sym), b, re.M)]
-    assert len(mine) == 1, sym
-    meta = {k: int(v) for k, v in re.findall(r'^\s*\.(\w+):\s+(\d+)\s*$', mine[0], re.M)}
+    out = []
+    for m in re.finditer(r'^(\w*%s\w*):' % fragment, text, re.M):
+        sym = m.group(1)
+        body = text[m.end():]
+        body = body[:body.index('s_endpgm')]
+        mine = [b for b in blocks if re.search(r'^\s*\.name:\s+%s\s*$' % re.escape(sym), b, re.M)]
+        assert len(mine) == 1, sym
+        out.append((sym, body, {k: int(v) for k, v in re.findall(r'^\s*\.(\w+):\s+(\d+)\s*$', mine[0], re.M)}))
+    assert out, fragment
+    return out
+
+
+def _kernel(text, fragment):
+    """-> (body, meta) of the one kernel whose mangled name contains `fragment`."""
+    (_, body, meta), = _kernels(text, fragment)
     return body, meta
 
 
@@ -68,14 +76,23 @@ def nr16(tmp_path_factory):
 SELF_MAX = re.compile(r'\bv_max_f32(?:_e32|_e64)?\s+v\d+,\s*(v\d+),\s*\1\b')
 
 
+def _footprint(meta, waves_per_simd, spills=0, scratch=0):
+    assert meta['vgpr_spill_count'] <= spills
+    assert meta['private_segment_fixed_size'] <= scratch
+    assert meta['vgpr_count'] <= 512 // waves_per_simd           # 512 registers per SIMD lane
+    assert meta['group_segment_fixed_size'] <= 163840 // waves_per_simd      # 4-wave workgroups: as many per CU (160 KiB of LDS)
+
+
 def _check(body, meta):
     # a ReLU of an accumulator is ONE instruction: no self-max that quiets a signalling NaN in front of it
     assert SELF_MAX.search('\tv_max_f32_e32 v0, v54, v54\n') and not SELF_MAX.search('\tv_max_f32_e32 v162, 0, v0\n')
     assert SELF_MAX.findall(body) == []
-    assert meta['vgpr_spill_count'] == 0
-    assert meta['private_segment_fixed_size'] == 0              # no scratch
-    assert meta['vgpr_count'] <= 256                            # two waves per SIMD
-    assert meta['group_segment_fixed_size'] <= 81920            # two workgroups per CU (160 KiB of LDS)
+    _footprint(meta, 2)          # no spill, no scratch, two waves per SIMD, two workgroups per CU
+
+
+def _ring(body):
+    """-> static (MFMAs, chunk barriers, LDS-DMA pieces) of a kernel"""
+    return tuple(len(re.findall(r'^\s*%s\b' % op, body, re.M)) for op in ('v_mfma_\\w+', 's_barrier', 'global_load_lds_dwordx4'))
 
 
 def test_m16_kernel(m16):
@@ -83,7 +100,46 @@ def test_m16_kernel(m16):
     _check(body, meta)
     # 7 200 executed per 16-sample tile; the six hidden layers share one unrolled body: no work added or lost
     assert len(re.findall(r'\bv_mfma_f32_16x16x4_f32\b', body)) == 2080
+    assert _ring(body) == (2080, 36, 152)
+    assert meta['group_segment_fixed_size'] == 78112             # 4 slots x 16 KiB + 3 144 floats of side data
 
 
 def test_nr16_kernel(nr16):
-    _check(*nr16)
+    body, meta = nr16
+    _check(body, meta)
+    assert len(re.findall(r'\bv_mfma_f32_16x16x4_f32\b', body)) == 1312
+    assert _ring(body) == (1312, 23, 52)
+    assert meta['group_segment_fixed_size'] == 37392             # 4 slots x 8 KiB + 1 156 floats of side data
+
+
+def test_split_and_trunk_kernels(tmp_path_factory):
+    """The other three kernels on the ring: footprints that fit their launch bounds."""
+    out = tmp_path_factory.mktemp('split')
+    split = _kernels(_compile('mlp.hip', out), 'canonical_mlp_split_lds_kernel')
+    assert len(split) == 3
+    for _, body, meta in split:                                  # __launch_bounds__(256, 1)
+        _footprint(meta, 1)
+        assert _ring(body)[1:] == (51, 212)
+    nr = _kernels(_compile('nonrigid.hip', out), 'nonrigid_split_kernel')
+    assert len(nr) == 4
+    for sym, body, meta in nr:                                   # __launch_bounds__(256, 2)
+        if 'F16x3ELb1E' in sym:      # the watched f16x3 instantiation is at the 256-register cap and spills (48 registers, 196 B)
+            _footprint(meta, 2, spills=48, scratch=196)
+        else:
+            _footprint(meta, 2)
+        assert _ring(body)[1:] == (24, 104)
+    (_, body, meta), = _kernels(_compile('trunks.hip', out), 'trunks_forward_kernel')      # __launch_bounds__(256, 1)
+    _footprint(meta, 1)
+    assert _ring(body) == (416, 28, 120)
+
+
+def test_one_lds_dma_statement():
+    """The LDS-DMA instruction is written in ONE place (weight_ring.h: glds16); comments may speak of it."""
+    holders = []
+    for name in sorted(os.listdir(CSRC)):
+        if not name.endswith(('.hip', '.h')):
+            continue
+        code = re.sub(r'//[^\n]*|/\*.*?\*/', '', open(os.path.join(CSRC, name)).read(), flags=re.S)
+        if 'global_load_lds_dwordx4' in code:
+            holders.append(name)
+    assert holders == ['weight_ring.h']
