@@ -862,6 +862,29 @@ int occnerf_mesh_resolve(const uint64_t *keys, const int32_t *faces, int64_t T, 
                          const uint8_t *vflag, const uint8_t *colors, const uint8_t *h_bgcolor, int32_t H, int32_t W,
                          uint8_t *cover, int32_t *tri, float *depth, uint8_t *rgb, int32_t *counts, void *stream);
 
+/* Collapsed samples, classified once in front of the kNN and feature kernels (no counterpart in the
+ * reference).  One lane per entry o of the live list rows[0 .. *n_dev) (capacity N_max): flag[o] = 1 iff xyz[rows[o]] lies
+ * inside the radius of center[4] (the |p - c|^2 < r^2 test of the kNN and feature kernels) AND the encoder input x[4] the
+ * feature kernel would form for it from the ten neighbours center_idx[0..9] is bitwise center_agg[36..39]; else 0.  For a
+ * flagged entry raw_c[o*5+4] = the signed distance the feature kernel would have written.  point_geo: occnerf_point_pack's
+ * records (P of them); center / center_idx: occnerf_knn_center's; center_agg: the 72 floats of
+ * occnerf_sample_features_centered. */
+int occnerf_center_classify(const float *xyz, const int32_t *rows, const int32_t *n_dev, int64_t N_max,
+                            const float *point_geo, int32_t P, const float *center, const int32_t *center_idx,
+                            const float *center_agg, float bound, float two_bound, uint8_t *flag, float *raw_c,
+                            void *stream);
+/* The list without its flagged entries, order preserved: keep[o2] = o (the unflagged list positions), rows2[o2] =
+ * rows[keep[o2]], *count2 their number, *taken = *n_dev - *count2; in_rows[o] = o2 for a kept entry, centre_row for a flagged
+ * one (the input row list of occnerf_canonical_mlp_rows and the split-operand kernels).  keep, rows2, in_rows: N_max entries.
+ * temp: occnerf_center_split_temp_bytes(N_max) bytes of device scratch. */
+int64_t occnerf_center_split_temp_bytes(int64_t N_max);
+int occnerf_center_split(const uint8_t *flag, const int32_t *rows, const int32_t *n_dev, int64_t N_max,
+                         int32_t centre_row, int32_t *keep, int32_t *rows2, int32_t *count2, int32_t *in_rows,
+                         int32_t *taken, void *temp, int64_t temp_bytes, void *stream);
+/* raw_c[keep[o2]*5+4] = raw2[o2*5+4] for o2 < *n2_dev: the kept entries' signed distance back at their list positions. */
+int occnerf_center_merge_dist(const float *raw2, const int32_t *keep, const int32_t *n2_dev, int64_t N_max, float *raw_c,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

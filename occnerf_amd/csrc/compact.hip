@@ -347,3 +347,62 @@ OCC_API int occnerf_scatter_raw(const float *raw_c, const int32_t *rows, const i
                        raw_full);
     return check_launch("scatter_raw");
 }
+
+// ---- collapsed samples out of the list (csrc/center.hip) ----------------------------------------------------------
+// From the flags of occnerf_center_classify over the live list rows[0 .. *n_dev), order preserved:
+//   keep[o2]  = o, the list positions that are NOT flagged, *count2 of them (hipCUB DeviceSelect);
+//   rows2[o2] = rows[keep[o2]] (ascending like rows: what the kNN and feature kernels run on);
+//   in_rows[o] = o2 for a kept entry (its row in the feature kernel's compact output), centre_row for a flagged one;
+//   *taken    = *n_dev - *count2.
+namespace occ {
+
+struct KeepPredicate {
+    const uint8_t *flag;
+    const int32_t *n_dev;
+    __device__ bool operator()(const int &o) const { return o < *n_dev && flag[o] == 0; }
+};
+
+__global__ void center_split_kernel(const uint8_t *__restrict__ flag, const int32_t *__restrict__ rows,
+                                    const int32_t *__restrict__ n_dev, const int32_t *__restrict__ keep,
+                                    const int32_t *__restrict__ count2, int32_t centre_row, int32_t *__restrict__ rows2,
+                                    int32_t *__restrict__ in_rows, int32_t *__restrict__ taken) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = *n_dev, n2 = *count2;
+    if (m == 0) *taken = (int32_t)(n - n2);
+    if (m < n && flag[m] != 0) in_rows[m] = centre_row;
+    if (m < n2) {                       // (keep[m] is an unflagged position: no entry of in_rows is written twice)
+        const int32_t o = keep[m];
+        rows2[m] = rows[o];
+        in_rows[o] = (int32_t)m;
+    }
+}
+
+}  // namespace occ
+
+OCC_API int64_t occnerf_center_split_temp_bytes(int64_t N) {
+    using namespace occ;
+    if (N <= 0 || N >= (1ll << 31)) return 0;
+    size_t bytes = 0;
+    hipcub::CountingInputIterator<int> it(0);
+    if (hipcub::DeviceSelect::If(nullptr, bytes, it, (int *)nullptr, (int *)nullptr, (int)N, KeepPredicate{nullptr, nullptr},
+                                 (hipStream_t)0) != hipSuccess)
+        return -1;
+    return (int64_t)bytes;
+}
+
+OCC_API int occnerf_center_split(const uint8_t *flag, const int32_t *rows, const int32_t *n_dev, int64_t N_max,
+                                 int32_t centre_row, int32_t *keep, int32_t *rows2, int32_t *count2, int32_t *in_rows,
+                                 int32_t *taken, void *temp, int64_t temp_bytes, void *stream) {
+    using namespace occ;
+    OCC_REQUIRE(flag && rows && n_dev && keep && rows2 && count2 && in_rows && taken && temp, "center_split: null argument");
+    OCC_REQUIRE(N_max > 0 && N_max < (1ll << 31), "center_split: N=%lld out of range", (long long)N_max);
+    size_t bytes = (size_t)temp_bytes;
+    hipcub::CountingInputIterator<int> it(0);
+    const hipError_t e = hipcub::DeviceSelect::If(temp, bytes, it, keep, count2, (int)N_max, KeepPredicate{flag, n_dev},
+                                                  as_stream(stream));
+    OCC_REQUIRE(e == hipSuccess, "center_split: %s", hipGetErrorString(e));
+    const int64_t blocks = (N_max + 255) / 256;
+    hipLaunchKernelGGL(center_split_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), flag, rows, n_dev, keep,
+                       count2, centre_row, rows2, in_rows, taken);
+    return check_launch("center_split");
+}

@@ -310,6 +310,31 @@ class Network(nn.Module):
             # frame -- and finding them, 1.7 ms, costs more than the kNN + feature work they save, 0.6 ms)
             if cfg.get('dedup_global_positions', False):
                 frows, fcount = ops.unique_heads(xyz, 3, frows, fcount, scan=scan_a, scan_count=count)
+        # Collapsed samples (csrc/center.hip; dedup off, the every-live-sample path): a sample inside the centre's radius whose
+        # encoder input is bitwise the centre's has the centre's whole feature row -- c's neighbour lists from the kNN kernel,
+        # c's 36 aggregate columns and c's 32 encoded ones from the feature kernel.  They are classified once, with a lane each,
+        # and leave the list those two kernels run on; the canonical MLP still evaluates every live sample and reads theirs
+        # from one centre row behind the compact rows (in_rows).  Same bits (cfg.center_split=False: the path without; tested).
+        # A radius of 0 flags nothing.  Counts stay on the device.  cfg.center_split: True / False, default 'auto' = on where
+        # the offsets come from the fp32 kernel the centre itself went through (or there are none).  The split-operand non-rigid
+        # kernels round differently: the collapsed samples then sit a few 1e-7 m off c, their signed distance differs from c's
+        # in its last bits, few are flagged and the stage costs more than it saves (profiles/r09_center_split.md).
+        split = None
+        self.last_center_taken = None
+        want = cfg.get('center_split', 'auto')
+        if want == 'auto':
+            want = pk['nr_bf16'] is None or bool(cfg.ignore_non_rigid_motions)
+        if not dedup and center is not None and len(center) > 2 and pack is not None and want and cfg.get('knn_query_list', True):
+            M = rows.shape[0]
+            raw_c = torch.empty(M, 5, device=xyz.device)
+            flag = ops.center_classify(xyz, rows, count, pack[0], center[0], center[1], center[2], ctx['bound32'],
+                                       ctx['two_bound32'], raw_c)
+            keep, frows, fcount, in_rows, taken = ops.center_split(flag, rows, count, M)
+            mlp_buf = torch.empty(M + 1, 68, device=xyz.device)
+            mlp_buf[M, :36] = center[2][:36]            # the layout of ops.center_row without the encoder input
+            mlp_buf[M, 36:] = center[2][40:72]
+            split = {'keep': keep, 'count2': fcount, 'in_rows': in_rows, 'raw_c': raw_c, 'mlp_buf': mlp_buf}
+            self.last_center_taken = taken
         self.last_head_counts = (fcount, None)
         if cfg.get('knn_query_list', True):    # tiles formed over the listed samples only (same indices, tested)
             knn = ops.msknn_clustered(xyz, rays8.shape[0], S, ctx['clusters'], ctx['seed'], rows=frows, count=fcount, center=center)
@@ -323,15 +348,19 @@ class Network(nn.Module):
             self.point_counter.detach(), table, ctx['bound32'], ctx['two_bound32'],
             enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale, enc.base_resolution,
             rows=frows, count=fcount, pack=pack, center=None if center is None else center[0],
-            center_agg=None if center is None else center[2])
+            center_agg=None if center is None else center[2], mlp_in_out=None if split is None else split['mlp_buf'])
         del knn
+        in_rows = None
+        if split is not None:       # the kept entries' distance joins the flagged ones': raw_c is complete, in list order
+            raw_c = ops.center_merge_dist(raw_c, split['keep'], split['count2'], split['raw_c'])
+            in_rows = split['in_rows']
         if dedup:
             scan_b, mrows, mcount, _ = ops.repeat_heads(mlp_in, 68, fcount)
             if cfg.get('dedup_global', True):       # ... and the repeats that are not neighbours in the list
                 mrows, mcount = ops.unique_heads(mlp_in, 68, mrows, mcount, scan=scan_b, scan_count=fcount)
             self.last_head_counts = (fcount, mcount)
         return {'dedup': dedup, 'rays8': rays8, 'z': z, 'mask': mask, 'rows': rows, 'count': count, 'mlp_in': mlp_in,
-                'raw_c': raw_c, 'scan_a': scan_a, 'scan_b': scan_b, 'mrows': mrows, 'mcount': mcount, 'cnl': pk['cnl'],
+                'raw_c': raw_c, 'in_rows': in_rows, 'scan_a': scan_a, 'scan_b': scan_b, 'mrows': mrows, 'mcount': mcount, 'cnl': pk['cnl'],
                 'cnl_bf16': pk['cnl_bf16'], 'domain_flag': pk['domain_flag'], 'N': xyz.shape[0]}
 
     @staticmethod
@@ -352,7 +381,7 @@ class Network(nn.Module):
             raw = ops.scatter_raw_heads(raw_h, st['raw_c'], st['rows'], st['count'], st['scan_a'], st['scan_b'],
                                         torch.zeros(N, 5, device=dev))
         else:
-            mlp(st['raw_c'], st['count'])
+            mlp(st['raw_c'], st['count'], st['in_rows'])      # (in_rows: the centre split's; None without it)
             raw = ops.scatter_raw(st['raw_c'], st['rows'], st['count'], torch.zeros(N, 5, device=dev))
         st['mlp_in'] = None
         return ops.composite(raw, st['mask'], st['z'], st['rays8'], bgcolor, out=out, out_rows=out_rows)[:3]

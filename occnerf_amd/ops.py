@@ -320,6 +320,66 @@ def scatter_raw(raw_c, rows, count, raw_full):
     return raw_full
 
 
+def center_classify(xyz, rows, count, geo, center, center_idx, center_agg, bound32, two_bound32, raw_c, flag=None):
+    """Collapsed samples of the live list rows[0 .. count) (csrc/center.hip): flag uint8[len(rows)] -- 1 where the sample lies
+    inside the radius of ops.knn_center's `center` AND its encoder input is bitwise the centre's (center_agg[36:40], ops.center_row):
+    its whole feature row is then the centre's.  raw_c[o, 4] receives the signed distance of the flagged entries.
+    geo: ops.point_pack's records.  Entries at and beyond count are left unwritten."""
+    M = rows.shape[0]
+    if flag is None:
+        flag = torch.empty(M, device=xyz.device, dtype=torch.uint8)
+    if flag.shape[0] < M or raw_c.shape[0] < M:
+        raise RuntimeError('center_classify: flag and raw_c need a row per list entry')
+    if center_idx.numel() < 10 or center_agg.numel() < 72 or center.numel() < 4:
+        raise RuntimeError('center_classify: center[4], center_idx[>= 10] and center_agg[72] (ops.knn_center, ops.center_row)')
+    with _guard(xyz):
+        rc = _lib.lib().occnerf_center_classify(
+            _chk(xyz, torch.float32, 'xyz'), _chk(rows, torch.int32, 'rows'), _chk(count, torch.int32, 'count'), M,
+            _chk(geo, torch.float32, 'point_geo'), int(geo.shape[0]), _chk(center, torch.float32, 'center'),
+            _chk(center_idx, torch.int32, 'center_idx'), _chk(center_agg, torch.float32, 'center_agg'),
+            float(bound32), float(two_bound32), _chk(flag, torch.uint8, 'flag'), _chk(raw_c, torch.float32, 'raw_c'),
+            _stream(xyz))
+    _lib.check(rc, 'center_classify')
+    return flag
+
+
+def center_split(flag, rows, count, centre_row):
+    """The live list without its flagged entries, order preserved (see the header) -> (keep int32[M], rows2 int32[M],
+    count2 int32[1], in_rows int32[M], taken int32[1]): rows2 / count2 for the kNN and feature kernels, in_rows for the
+    canonical MLP (a flagged entry reads row `centre_row` of its input), keep for center_merge_dist.  No sync."""
+    M, dev = rows.shape[0], rows.device
+    keep = torch.empty(M, device=dev, dtype=torch.int32)
+    rows2 = torch.empty(M, device=dev, dtype=torch.int32)
+    in_rows = torch.empty(M, device=dev, dtype=torch.int32)
+    count2 = torch.empty(1, device=dev, dtype=torch.int32)
+    taken = torch.empty(1, device=dev, dtype=torch.int32)
+    if M == 0:
+        count2.zero_()
+        taken.zero_()
+        return keep, rows2, count2, in_rows, taken
+    nbytes = int(_lib.lib().occnerf_center_split_temp_bytes(M))
+    if nbytes < 0:
+        raise RuntimeError('center_split: temp size query failed')
+    temp = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    with _guard(rows):
+        rc = _lib.lib().occnerf_center_split(
+            _chk(flag, torch.uint8, 'flag'), _chk(rows, torch.int32, 'rows'), _chk(count, torch.int32, 'count'), M,
+            int(centre_row), keep.data_ptr(), rows2.data_ptr(), count2.data_ptr(), in_rows.data_ptr(), taken.data_ptr(),
+            temp.data_ptr(), nbytes, _stream(rows))
+    _lib.check(rc, 'center_split')
+    return keep, rows2, count2, in_rows, taken
+
+
+def center_merge_dist(raw2, keep, count2, raw_c):
+    """raw_c[keep[o2], 4] = raw2[o2, 4] for o2 < count2: the kept entries' signed distance back at their list positions."""
+    with _guard(raw2):
+        rc = _lib.lib().occnerf_center_merge_dist(
+            _chk(raw2, torch.float32, 'raw2'), _chk(keep, torch.int32, 'keep'), _chk(count2, torch.int32, 'count2'),
+            keep.shape[0], _chk(raw_c, torch.float32, 'raw_c'), _stream(raw2))
+    _lib.check(rc, 'center_merge_dist')
+    return raw_c
+
+
 def repeat_heads(keys, key_cols, count, rows=None, want_mask=False):
     """Run-length elimination of repeated samples (see the header): keys float32/int32 [M, C] (row-contiguous), the first
     key_cols columns compared as bit patterns; entry m is row rows[m] (rows given) or m, for m < count[0] (device).
@@ -581,8 +641,10 @@ def center_row(mlp_in_row, enc_in_row):
 
 def sample_features(xyz, knn_idxs, point_base, normals, unit, counter, table, bound32, two_bound32,
                     embeddings, offsets, S, H, raw=None, want_enc_in=False, geo_idxs=None,
-                    att_in=None, rows=None, count=None, pack=None, center=None, center_agg=None):
+                    att_in=None, rows=None, count=None, pack=None, center=None, center_agg=None, mlp_in_out=None):
     """rows (int32[M], optional): compact list of samples to evaluate; outputs then have M rows.
+    mlp_in_out (float32[>= M, 68], optional): the buffer the feature rows are written to, and returned as mlp_in, instead of a
+    fresh [M, 68] one (a caller that keeps further rows behind them: Network's centre row).
     center / center_agg (optional, renderer's path): ops.knn_center's [4] and ops.center_row of a sample with the centre's
     neighbour lists -- groups of samples inside the radius copy its aggregate columns instead of gathering rows, and its encoded
     columns too when their encoder input is bitwise the centre's (same bits).  FRESHNESS CONTRACT (not checkable here):
@@ -601,7 +663,12 @@ def sample_features(xyz, knn_idxs, point_base, normals, unit, counter, table, bo
     geo, tail = pack if pack is not None else (None, None)
     if table.dim() != 2 or table.shape[1] != table_stride():
         raise RuntimeError(f'sample_features: table must be [P,{table_stride()}] (ops.point_table), got {tuple(table.shape)}')
-    mlp_in = torch.empty(N, 68, device=dev, dtype=torch.float32)
+    if mlp_in_out is None:
+        mlp_in = torch.empty(N, 68, device=dev, dtype=torch.float32)
+    else:
+        mlp_in = mlp_in_out
+        if mlp_in.dim() != 2 or mlp_in.shape[0] < N or mlp_in.shape[1] != 68:
+            raise RuntimeError(f'sample_features: mlp_in_out must be [>= {N}, 68], got {tuple(mlp_in.shape)}')
     raw = torch.empty(N, 5, device=dev, dtype=torch.float32) if raw is None else raw
     enc_in = torch.empty(N, 4, device=dev, dtype=torch.float32) if want_enc_in else None
     with _guard_dev(dev):
@@ -617,7 +684,7 @@ def sample_features(xyz, knn_idxs, point_base, normals, unit, counter, table, bo
             _opt(geo, torch.float32, 'point_geo'), _opt(tail, torch.float32, 'point_tail'),
             0 if geo is None else int(geo.shape[0]),
             _opt(center, torch.float32, 'center'), _opt(center_agg, torch.float32, 'center_agg'),
-            mlp_in.data_ptr(), _chk(raw, torch.float32, 'raw'),
+            _chk(mlp_in, torch.float32, 'mlp_in'), _chk(raw, torch.float32, 'raw'),
             None if enc_in is None else enc_in.data_ptr(), _stream(xyz))
     _lib.check(rc, 'sample_features')
     return mlp_in, raw, enc_in
