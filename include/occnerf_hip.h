@@ -885,6 +885,41 @@ int occnerf_center_split(const uint8_t *flag, const int32_t *rows, const int32_t
 int occnerf_center_merge_dist(const float *raw2, const int32_t *keep, const int32_t *n2_dev, int64_t N_max, float *raw_c,
                               void *stream);
 
+/* The geometry the volume renderer sees, per pixel (occnerf_amd/gbuffer.py, run.py show_depth / show_normal / show_shaded /
+ * geometry.save).  The reference has no counterpart of these two entries: it drops the compositor's
+ * depth.  Everything is float32 with one rounding per operator, division and square root correctly rounded; no atomics, no
+ * host wait: bit-identical to tests/gbuffer_restatement.py and the same bytes on every run.  Limits: height * width < 2^31
+ * and R <= height * width.
+ *
+ * ray_index[R] int64 ascending: the flat pixel of every ray (as occnerf_assemble_image takes it); rays[2,R,3]: origins o and
+ * unnormalised directions d; depth[R], alpha[R]: the compositor's sum of w z and sum of w.
+ * A pixel with ray r is depth-valid iff alpha[r] >= min_alpha, alpha[r] > 0 and both values are finite.  Then
+ * t = depth[r] / alpha[r] -- the ray PARAMETER (the reference's depth; the metric distance is t |d|) -- and
+ * P_c = o_c + t d_c (product, then sum). */
+
+/* No counterpart in the reference.  One thread per pixel, its ray found by occnerf_assemble_image's binary search ->
+ * points[H,W,4] (P, t; zeros where the pixel has no ray or is not depth-valid), valid[H,W] uint8 (bit 0: depth-valid),
+ * pix_ray[H,W] int32 (the row r of a depth-valid pixel, else -1).  R = 0: the pointers of the four ray arrays may be NULL. */
+int occnerf_gbuffer_points(const int64_t *ray_index, int64_t R, const float *rays, const float *depth, const float *alpha,
+                           float min_alpha, int32_t height, int32_t width, float *points, uint8_t *valid, int32_t *pix_ray,
+                           void *stream);
+/* No counterpart in the reference.  points / pix_ray: occnerf_gbuffer_points' of the same rays.  Per depth-valid pixel (i, j):
+ * the horizontal secant a is P(i,j+1) - P (right) or P - P(i,j-1) (left), a candidate existing iff its neighbour is inside
+ * the image and depth-valid; of two the one with the smaller |dt| is taken, a tie goes to the right one.  The vertical secant
+ * b alike from P(i+1,j) - P (down; it takes the tie) and P - P(i-1,j).  Without a candidate for either the normal is invalid.
+ * n = a x b (per component two rounded products and their difference); s = (n_x d_x + n_y d_y) + n_z d_z with the pixel's own
+ * d; s > 0: n = -n (towards the camera); l2 = (n_x^2 + n_y^2) + n_z^2, zero or not finite: invalid; else n = n / sqrt(l2) and
+ * shade = clamp01(-((n_x d_x + n_y d_y) + n_z d_z) / sqrt((d_x^2 + d_y^2) + d_z^2)), clamp01(x) = min(max(x, 0), 1) and 0
+ * for NaN.  The normal is in the space of the rays and is not rotated.
+ * -> normal[H,W,3] (zeros where invalid), valid[H,W] uint8 (bit 0 depth-valid, bit 1 normal valid; every byte is written
+ * whole and none is read, so occnerf_gbuffer_points' valid may be passed and is finished in place), and the 8-bit panels [H,W,3] through the quantisation of occnerf_assemble_image, each NULL when not wanted:
+ * depth_u8 grey clamp01((t_hi - t) / (t_hi - t_lo)) with t_range[2] = (t_lo, t_hi) read from DEVICE memory (NULL only with
+ * depth_u8 NULL); normal_u8 0.5 n_c + 0.5; shaded_u8 grey shade.  A pixel that is not depth-valid (depth_u8) or has no
+ * valid normal (normal_u8, shaded_u8) gets the HOST h_bgcolor01[3].  R = 0: rays may be NULL. */
+int occnerf_gbuffer_normals(const float *points, const int32_t *pix_ray, const float *rays, int64_t R, int32_t height,
+                            int32_t width, const float *t_range, const float *h_bgcolor01, float *normal, uint8_t *valid,
+                            uint8_t *depth_u8, uint8_t *normal_u8, uint8_t *shaded_u8, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ SIGNATURES = {
     'occnerf_center_split_temp_bytes': (_i64, [_i64]),
     'occnerf_center_split': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'occnerf_center_merge_dist': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    'occnerf_gbuffer_points': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'occnerf_gbuffer_normals': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -145,6 +145,14 @@ _DEFAULTS = {
     # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the
     # mesh render beside the photograph.  The frames are posed with the mesh_pose keys
     'mesh_view': {'frames': None, 'panels': True},
+    # run.py tpose / freeview / backview / movement / allview, the geometry the volume renderer sees (occnerf_amd/gbuffer.py,
+    # DESIGN.md section 7k): show_depth / show_normal / show_shaded add a panel each behind [rgb, truth, alpha].
+    # geometry.min_alpha: a pixel has a depth where its accumulated alpha reaches this; geometry.depth_range: [t_lo, t_hi] of
+    # the depth panel's grey, None: the frame's own near.min() .. far.max() (it follows the frame's box, so the grey of a
+    # movement sequence flickers: fix the range there); geometry.save: also write each frame's t, normal, valid and t_range
+    # to <folder>_geometry/<name>.npz.  t is the ray parameter of the unnormalised rays, the metric distance is t |d|
+    'show_depth': False, 'show_normal': False, 'show_shaded': False,
+    'geometry': {'min_alpha': 0.5, 'depth_range': None, 'save': False},
 }
 # resolution + 1 points on the longest axis, at most as many on the others: the default grid stays below the kernels' 2^31
 assert (_DEFAULTS['mesh']['resolution'] + 1) ** 3 < 1 << 31

@@ -55,6 +55,14 @@ def assemble_uint8_device(width, height, ray_index, bgcolor, rgb, alpha, want_al
     return out, out_a
 
 
+class _NpzJob:
+    """A queue item of ImageWriter.append_device_npz: {key: pinned stage}, the event behind their copies, the file."""
+    __slots__ = ('stages', 'event', 'path')
+
+    def __init__(self, stages, event, path):
+        self.stages, self.event, self.path = stages, event, path
+
+
 class ImageWriter:
     """PNG dump with the reference's folder layout (image_util.py:53-75): <output_dir>/<exp_name>/NNNNNN.png,
     directory recreated on start.  `append` takes a host array like the reference's; `append_device` takes a uint8
@@ -84,6 +92,9 @@ class ImageWriter:
             job = self._jobs.get()
             if job is None:
                 return
+            if isinstance(job, _NpzJob):                        # append_device_npz; an image job is a plain tuple
+                self._write_npz(job.stages, job.event, job.path)
+                continue
             image, event, name, stage = job
             try:
                 if event is not None:
@@ -119,6 +130,35 @@ class ImageWriter:
         event.record(torch.cuda.current_stream(image_u8.device))
         self._jobs.put((stage, event, name, stage))
         return self.frame_idx, name
+
+    def _write_npz(self, stages, event, path):
+        try:
+            event.synchronize()
+            np.savez(path, **{k: st.numpy() for k, st in stages.items()})
+        except Exception as e:                                  # surfaced by finalize()
+            self._error = e
+        for st in stages.values():
+            self._free[(tuple(st.shape), st.dtype)].put(st)
+
+    def append_device_npz(self, arrays, path):
+        """arrays: {key: GPU tensor} -> the numpy archive `path` (np.savez: not compressed), by the same scheme as
+        append_device: every tensor is copied into a pinned staging buffer of its shape and dtype without blocking the caller,
+        one event is recorded behind the copies, and the writer thread waits for it and writes the file.  Returns at once."""
+        stages, dev = {}, None
+        for k, t in arrays.items():
+            key = (tuple(t.shape), t.dtype)
+            pool = self._stages.setdefault(key, [])
+            free = self._free.setdefault(key, self._queue_cls())
+            if len(pool) < self._n_stages:
+                stage = torch.empty(key[0], dtype=t.dtype).pin_memory()
+                pool.append(stage)
+            else:
+                stage = free.get()                              # blocks only when the writer is `stages` frames behind
+            stage.copy_(t, non_blocking=True)
+            stages[k], dev = stage, t.device
+        event = torch.cuda.Event()
+        event.record(torch.cuda.current_stream(dev))
+        self._jobs.put(_NpzJob(stages, event, path))
 
     def finalize(self):
         self._jobs.put(None)

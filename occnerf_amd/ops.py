@@ -1562,3 +1562,92 @@ def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
                                              tri.data_ptr(), depth.data_ptr(), rgb.data_ptr(), pn, _stream(faces))
     _lib.check(rc, 'mesh_resolve')
     return cover, tri, depth, rgb
+
+
+# ------------------------------------------------------------------ geometry maps of a rendered frame
+GBUFFER_PANELS = ('depth', 'normal', 'shaded')
+GBUFFER_MAX_PIXELS = 1 << 31
+
+
+def _gbuffer_rays(who, rays, dev):
+    pr = _chk(rays, torch.float32, f'{who}: rays')
+    if rays.dim() != 3 or rays.shape[0] != 2 or rays.shape[2] != 3 or rays.device != dev:
+        raise RuntimeError(f'{who}: rays must be float32 [2,R,3] on {dev}, got {tuple(rays.shape)} on {rays.device}')
+    return pr, int(rays.shape[1])
+
+
+def gbuffer_points(ray_index, rays, depth, alpha, min_alpha, height, width):
+    """The surface point of every pixel's ray (occnerf_gbuffer_points): ray_index int64 [R] ascending flat pixels, rays float32
+    [2,R,3], depth / alpha float32 [R] on one device -> (points float32 [H,W,4]: o + t d and t = depth / alpha, zeros where the
+    pixel has no ray or alpha < min_alpha, alpha <= 0 or a value is not finite; valid uint8 [H,W]: bit 0; pix_ray int32 [H,W]:
+    the ray's row, -1 where not valid)."""
+    H, W = int(height), int(width)
+    if H <= 0 or W <= 0 or H * W >= GBUFFER_MAX_PIXELS:
+        raise RuntimeError(f'gbuffer_points: height = {H}, width = {W} must be positive with fewer than 2^31 pixels')
+    pi = _chk(ray_index, torch.int64, 'gbuffer_points: ray_index')
+    dev = ray_index.device
+    pr, R = _gbuffer_rays('gbuffer_points', rays, dev)
+    pd, pa = _chk(depth, torch.float32, 'gbuffer_points: depth'), _chk(alpha, torch.float32, 'gbuffer_points: alpha')
+    if tuple(ray_index.shape) != (R,) or tuple(depth.shape) != (R,) or tuple(alpha.shape) != (R,) or \
+            not (depth.device == alpha.device == dev):
+        raise RuntimeError(f'gbuffer_points: ray_index, depth and alpha must be [{R}] like rays, on {dev}; got '
+                           f'{tuple(ray_index.shape)}, {tuple(depth.shape)}, {tuple(alpha.shape)}')
+    if R > H * W:
+        raise RuntimeError(f'gbuffer_points: R = {R} is larger than height * width = {H * W}')
+    points = torch.empty(H, W, 4, device=dev, dtype=torch.float32)
+    valid = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    pix_ray = torch.empty(H, W, device=dev, dtype=torch.int32)
+    with _guard_dev(dev):
+        rc = _lib.lib().occnerf_gbuffer_points(pi if R else None, R, pr if R else None, pd if R else None, pa if R else None,
+                                               float(min_alpha), H, W, points.data_ptr(), valid.data_ptr(), pix_ray.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, 'gbuffer_points')
+    return points, valid, pix_ray
+
+
+def gbuffer_normals(points, pix_ray, rays, t_range, bgcolor01, panels=GBUFFER_PANELS, valid=None):
+    """Normals from the point map's secants, and the panels (occnerf_gbuffer_normals): points / pix_ray of gbuffer_points and
+    the same rays; t_range float32 [2] ON THE DEVICE (t_lo, t_hi), None allowed without the depth panel; bgcolor01: 3 host
+    floats -> (normal float32 [H,W,3], valid uint8 [H,W] with bit 0 depth-valid and bit 1 normal valid, {name: uint8 [H,W,3]}
+    for the names in `panels`, a subset of GBUFFER_PANELS).  valid: gbuffer_points' uint8 [H,W] to finish in place (every
+    thread writes its own byte whole and reads none); None allocates one."""
+    pp = _chk(points, torch.float32, 'gbuffer_normals: points')
+    if points.dim() != 3 or points.shape[2] != 4:
+        raise RuntimeError(f'gbuffer_normals: points must be float32 [H,W,4], got {tuple(points.shape)}')
+    H, W = int(points.shape[0]), int(points.shape[1])
+    if H <= 0 or W <= 0 or H * W >= GBUFFER_MAX_PIXELS:
+        raise RuntimeError(f'gbuffer_normals: height = {H}, width = {W} must be positive with fewer than 2^31 pixels')
+    dev = points.device
+    pq = _chk(pix_ray, torch.int32, 'gbuffer_normals: pix_ray')
+    if tuple(pix_ray.shape) != (H, W) or pix_ray.device != dev:
+        raise RuntimeError(f'gbuffer_normals: pix_ray must be int32 [{H},{W}] on {dev}, got {tuple(pix_ray.shape)} on {pix_ray.device}')
+    pr, R = _gbuffer_rays('gbuffer_normals', rays, dev)
+    if R > H * W:
+        raise RuntimeError(f'gbuffer_normals: R = {R} is larger than height * width = {H * W}')
+    panels = tuple(panels)
+    unknown = [k for k in panels if k not in GBUFFER_PANELS]
+    if unknown:
+        raise RuntimeError(f'gbuffer_normals: unknown panel {unknown[0]!r}; the panels are {GBUFFER_PANELS}')
+    pt = None
+    if 'depth' in panels:
+        if t_range is None:
+            raise RuntimeError('gbuffer_normals: the depth panel needs t_range')
+        pt = _chk(t_range, torch.float32, 'gbuffer_normals: t_range')
+        if t_range.numel() != 2 or t_range.device != dev:
+            raise RuntimeError(f'gbuffer_normals: t_range must be float32 [2] on {dev}, got {tuple(t_range.shape)} on {t_range.device}')
+    _bg, pbg = _host_f32(bgcolor01, 3)
+    normal = torch.empty(H, W, 3, device=dev, dtype=torch.float32)
+    if valid is None:
+        valid = torch.empty(H, W, device=dev, dtype=torch.uint8)
+    else:
+        _chk(valid, torch.uint8, 'gbuffer_normals: valid')
+        if tuple(valid.shape) != (H, W) or valid.device != dev:
+            raise RuntimeError(f'gbuffer_normals: valid must be uint8 [{H},{W}] on {dev}, got {tuple(valid.shape)} on {valid.device}')
+    out = {k: torch.empty(H, W, 3, device=dev, dtype=torch.uint8) for k in GBUFFER_PANELS if k in panels}
+    ptr = {k: (out[k].data_ptr() if k in out else None) for k in GBUFFER_PANELS}
+    with _guard_dev(dev):
+        rc = _lib.lib().occnerf_gbuffer_normals(pp, pq, pr if R else None, R, H, W, pt, pbg, normal.data_ptr(), valid.data_ptr(),
+                                                ptr['depth'], ptr['normal'], ptr['shaded'],
+                                                torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, 'gbuffer_normals')
+    return normal, valid, out

@@ -105,6 +105,9 @@ def render_sequence(renderer, loader, data_type, iter_val, on_frame, device='cud
 
     with torch.no_grad():
         for data, key, meta in frames_to_device(loader, data_type, device):
+            # the geometry maps (occnerf_amd/gbuffer.py) take the frame's rays and the extremes of its near / far: references
+            # to the renderer's own inputs, added here for every route of frames_to_device alike; nothing is copied or reduced
+            meta = dict(meta, rays=data['rays'], near=data['near'], far=data['far'])
             cur = renderer.submit(data, iter_val=iter_val, ray_order_key=key)
             if prev is not None:
                 deliver(*prev)

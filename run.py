@@ -7,6 +7,8 @@ exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seed
 seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on disk.  `--type mesh` writes no frames but
 <...>/<load_net>/mesh/mesh.ply and mesh.json; with `mesh_pose.frames` also mesh/posed/<frame name>.ply and mesh/posed.json;
 with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json (run_mesh below).
+`show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
+`geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
 
 Several GPUs: start it under torchrun, one process per GPU --
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run.py --cfg ... --type movement
@@ -93,6 +95,31 @@ def _render(data_type, folder_name):
     writer = ImageWriter(output_dir=os.path.join(cfg.logdir, str(cfg.load_net).replace(':', '_')),
                          exp_name=folder_name) if rank == 0 else None
     stats = {'rays': 0, 'first_s': 0.0, 'per_frame': [], 'frames': 0}
+    # the geometry the renderer sees (occnerf_amd/gbuffer.py): the panels behind [rgb, truth, alpha] and
+    # the raw maps in the sibling folder <folder>_geometry; every key defaults to off and nothing below runs then
+    geo = cfg.get('geometry') or {}
+    geo_panels = [k for k in ('depth', 'normal', 'shaded') if cfg.get(f'show_{k}')]
+    geo_dir = None
+    if rank == 0 and os.path.isdir(writer.image_dir + '_geometry'):
+        # the image folder was just recreated: an earlier run's raw maps beside it no longer belong to its PNGs
+        import shutil
+        shutil.rmtree(writer.image_dir + '_geometry')
+    if rank == 0 and geo.get('save'):
+        geo_dir = writer.image_dir + '_geometry'
+        os.makedirs(geo_dir)
+        import json
+        with open(os.path.join(geo_dir, 'geometry.json'), 'w') as f:      # the sidecar: what the arrays of every <name>.npz mean
+            json.dump({'t': 'float32 [H,W]: the ray PARAMETER depth / alpha of the composited depth (the reference\'s depth); '
+                            'the rays are not normalised, the metric distance is t * |d|; 0 where valid bit 0 is clear',
+                       'normal': 'float32 [H,W,3]: unit normal facing the camera, in the space of the rays (the body space of '
+                                 'the frame\'s camera matrix E), not rotated into the camera; 0 where valid bit 1 is clear',
+                       'valid': 'uint8 [H,W]: bit 0 the pixel has a depth (alpha >= min_alpha, alpha > 0, finite values), '
+                                'bit 1 it has a normal',
+                       't_range': 'float32 [2]: (t_lo, t_hi) of the depth panel\'s grey (t_hi - t) / (t_hi - t_lo)',
+                       'min_alpha': float(geo.get('min_alpha', 0.5)),
+                       'depth_range': 'per frame: near.min() .. far.max()' if geo.get('depth_range') is None
+                       else [float(v) for v in geo.depth_range],
+                       'definition': 'DESIGN.md section 7k'}, f, indent=1)
     torch.cuda.synchronize()
     t_wall0 = time.perf_counter()
 
@@ -104,10 +131,23 @@ def _render(data_type, folder_name):
         # photograph as 8-bit pixels, where the loader has one (a prepared dataset; tpose has none)
         panels = [rgb_img] + ([meta['truth_u8']] if cfg.show_truth and 'truth_u8' in meta else []) + \
             ([alpha_img] if cfg.show_alpha else [])
+        maps = None
+        if geo_panels or geo_dir:
+            # [rgb, truth, alpha, depth, normal, shaded]: two launches on what rank 0 holds after the gather; the depth range
+            # is geometry.depth_range or the frame's own near.min() .. far.max(), reduced on the device
+            from occnerf_amd.gbuffer import geometry_maps
+            maps = geometry_maps(meta['width'], meta['height'], meta['ray_index'], meta['rays'].to(dev, non_blocking=True),
+                                 out['depth'], out['alpha'], min_alpha=float(geo.get('min_alpha', 0.5)),
+                                 t_range=geo.get('depth_range'), bgcolor=np.array(cfg.bgcolor) / 255., panels=geo_panels,
+                                 near=meta['near'].to(dev, non_blocking=True), far=meta['far'].to(dev, non_blocking=True))
+            panels += [maps[f'{k}_u8'] for k in geo_panels]
         img_dev = torch.cat(panels, dim=1) if len(panels) > 1 else rgb_img
         # uint8 over PCIe into a pinned staging buffer; the writer thread waits for the copy and encodes the PNG
         # while the next frame renders (nothing here blocks on the GPU)
-        writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type in ('movement', 'backview') else None)
+        _, name = writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type in ('movement', 'backview') else None)
+        if geo_dir:                                        # the raw maps, by the same writer thread and staging scheme
+            writer.append_device_npz({k: maps[k] for k in ('t', 'normal', 'valid', 't_range')},
+                                     os.path.join(geo_dir, f'{name}.npz'))
         stats['rays'] += int(meta['ray_index'].numel())
         stats['per_frame'].append(int(meta['ray_index'].numel()))
         stats['frames'] += 1
