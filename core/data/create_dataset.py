@@ -19,12 +19,15 @@ and the SMPL model are not redistributable, tools/make_synthetic_dataset.py writ
   * 'freeview' / 'backview' / 'allview' / 'tpose': the cameras derived from a dataset frame (occnerf_amd.views.ViewFrames,
     the reference's freeview.py / backview.py / allview.py / tpose.py).  Host dicts when iterated; `device_frames` builds
     the rays on the GPU (csrc/view.hip), one frame ahead in the same way.  backview reads the directory movement would;
-    allview also needs all_cameras.pkl."""
+    allview also needs all_cameras.pkl;
+  * 'animate': the subject of the directory movement would read, driven by the motion `animate.motion` names
+    (occnerf_amd.animate.AnimateFrames; the reference has no such type).  A prepared dataset only."""
 import os
 
 import torch
 
 from configs import cfg
+from occnerf_amd.animate import AnimateFrames
 from occnerf_amd.dataset import PreparedDataset, WholeFrames, loader_from_cfg, resolve_dataset_path
 from occnerf_amd.sequence import SyntheticFrames
 from occnerf_amd.views import KINDS as VIEW_KINDS, ViewFrames
@@ -39,9 +42,11 @@ def _prepared(data_type, evaluate, path):
                                prefetch=bool(dict(cfg.get('train', {})).get('prefetch', True)))
     if data_type in VIEW_KINDS:
         return ViewFrames.from_cfg(cfg, path, data_type, prepare_device=device)
+    if data_type == 'animate':
+        return AnimateFrames.from_cfg(cfg, path, prepare_device=device)
     if data_type not in ('movement', 'progress'):
         raise NotImplementedError(f"type '{data_type}' on the prepared dataset '{path}': train, movement, progress, "
-                                  'freeview, backview, allview and tpose read a dataset')
+                                  'freeview, backview, allview, tpose and animate read a dataset')
     skip, maxframes = 1, -1
     if data_type == 'progress':
         total = len([f for f in os.listdir(os.path.join(path, 'images')) if f.endswith('.png')])
@@ -53,10 +58,13 @@ def _prepared(data_type, evaluate, path):
 
 
 def create_dataloader(data_type='train', evaluate=False, **_):
-    # backview has no dataset node of its own in the reference's configs: it reads the directory movement would
-    path = resolve_dataset_path(cfg, 'movement' if data_type == 'backview' else data_type)
+    # backview has no dataset node of its own in the reference's configs: it reads the directory movement would; so does animate
+    path = resolve_dataset_path(cfg, 'movement' if data_type in ('backview', 'animate') else data_type)
     if path is not None:
         return _prepared(data_type, evaluate, path)
+    if data_type == 'animate':
+        raise NotImplementedError('--type animate drives the subject of a prepared dataset; the synthetic frame source has '
+                                  'none (set train.dataset_path or movement.dataset)')
     if cfg.get('dataset', 'synthetic') != 'synthetic' or \
             data_type not in ('tpose', 'freeview', 'movement', 'allview', 'progress'):
         raise NotImplementedError(

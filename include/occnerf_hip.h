@@ -920,6 +920,26 @@ int occnerf_gbuffer_normals(const float *points, const int32_t *pix_ray, const f
                             int32_t width, const float *t_range, const float *h_bgcolor01, float *normal, uint8_t *valid,
                             uint8_t *depth_u8, uint8_t *normal_u8, uint8_t *shaded_u8, void *stream);
 
+/* The driving skeleton of an animate frame as an 8-bit panel (occnerf_amd/skeleton.py, run.py --type animate show_skeleton;
+ * DESIGN.md section 7l).  No counterpart in the reference.  Everything is float64 with one rounding per operator and a
+ * correctly rounded division; one launch, one thread per pixel, no atomics: bit-identical to tests/skeleton_restatement.py
+ * and the same bytes on every run.  All arguments but img and record are HOST pointers, taken by value at the call.
+ *
+ * h_joints[24,3] float32 in the space of the rays; h_K[3,3] (K[0,1] != 0 is refused), h_E[4,4] float64: camera point
+ * c = ((E_r0 x + E_r1 y) + E_r2 z) + E_r3 per row r, u = (K00 c_0) / c_2 + K02, v = (K11 c_1) / c_2 + K12.  A joint with a
+ * non-finite c, u or v or with c_2 <= 0 is dropped with the bones that end in it.  Primitive q < 23 is the bone from joint
+ * a = q + 1 to its SMPL parent b with radius bone_px and depth key (c_2(a) + c_2(b)) * 0.5; primitive 23 + k is the disc of
+ * joint k with radius 1.5 * bone_px and key c_2(k).  Pixel (i, j) is sampled at p = (j, i): with ab = b - a and l2 = ab.ab,
+ * s = ((p - a).ab) / l2 clamped to 0..1 (l2 == 0: the disc about a), the sample is covered iff |p - (a + s ab)|^2 <= r^2.
+ * Among the covering primitives the smallest key wins, at equal keys the higher index; the pixel gets h_palette[24,3] of the
+ * bone's child joint a (of the disc's joint), an uncovered one h_bgcolor[3].
+ * -> img[H,W,3] uint8 and record[1 + occnerf_skeleton_panel_blocks(H, W)] int32: record[0] the joints dropped, record[1 + g]
+ * the pixels workgroup g covered (the host adds them).  Limits: H, W >= 1, H * W < 2^31, 0 <= bone_px <= 1e6. */
+int32_t occnerf_skeleton_panel_blocks(int32_t height, int32_t width);
+int occnerf_skeleton_panel(const float *h_joints, const double *h_K, const double *h_E, double bone_px,
+                           const uint8_t *h_palette, const uint8_t *h_bgcolor, int32_t height, int32_t width, uint8_t *img,
+                           int32_t *record, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

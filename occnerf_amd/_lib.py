@@ -156,6 +156,8 @@ SIGNATURES = {
     'occnerf_center_merge_dist': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp]),
     'occnerf_gbuffer_points': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'occnerf_gbuffer_normals': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'occnerf_skeleton_panel_blocks': (_i32, [_i32, _i32]),
+    'occnerf_skeleton_panel': (C.c_int, [_vp, _vp, _vp, C.c_double, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
 }
 
 _lib = None

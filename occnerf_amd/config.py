@@ -153,6 +153,16 @@ _DEFAULTS = {
     # to <folder>_geometry/<name>.npz.  t is the ray parameter of the unnormalised rays, the metric distance is t |d|
     'show_depth': False, 'show_normal': False, 'show_shaded': False,
     'geometry': {'min_alpha': 0.5, 'depth_range': None, 'save': False},
+    # run.py --type animate (occnerf_amd/animate.py): the subject of the movement source's prepared dataset
+    # driven by animate.motion, a prepared dataset directory (only its mesh_infos.pkl is read) or an .npz with poses [T,72] and
+    # optionally Rh / Th.  frame_idx: the subject's source frame (its skeleton, its calibrated camera, where the motion is put);
+    # substeps n: n - 1 slerped frames between consecutive frames of the motion; align: map the motion's frame 0 onto the
+    # source frame's Rh / Th (False: take Rh / Th as they are -- a motion of the subject's own capture); camera: 'fixed' (the
+    # body moves through the image), 'follow' (it turns on the spot) or 'orbit' (follow, the camera turning as freeview's
+    # does, one turn in render_frames frames); bone_px: a bone's half-width in the skeleton panel.  show_skeleton: the
+    # driving skeleton from the frame's camera as a panel directly behind rgb (occnerf_amd/skeleton.py); animate only
+    'animate': {'motion': None, 'frame_idx': 0, 'substeps': 1, 'align': True, 'camera': 'fixed', 'bone_px': 3.0},
+    'show_skeleton': False,
 }
 # resolution + 1 points on the longest axis, at most as many on the others: the default grid stays below the kernels' 2^31
 assert (_DEFAULTS['mesh']['resolution'] + 1) ** 3 < 1 << 31

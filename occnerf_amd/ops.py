@@ -1651,3 +1651,44 @@ def gbuffer_normals(points, pix_ray, rays, t_range, bgcolor01, panels=GBUFFER_PA
                                                 torch.cuda.current_stream(dev).cuda_stream)
     _lib.check(rc, 'gbuffer_normals')
     return normal, valid, out
+
+
+# ------------------------------------------------------------------ the driving skeleton of an animate frame
+SKELETON_JOINTS = 24
+
+
+def skeleton_panel(joints, K, E, height, width, bone_px, palette, bgcolor_u8, device):
+    """The skeleton panel of one frame (occnerf_skeleton_panel): joints [24,3] float32 in the space of the rays, K [3,3] and E
+    [4,4] (taken as float64), bone_px the half-width of a bone in pixels, palette uint8 [24,3], bgcolor_u8 3 bytes -- all on the
+    HOST, taken by value -> (img uint8 [H,W,3], record int32 [1 + workgroups]) on `device`: record[0] the joints dropped,
+    record[1:] the pixels each workgroup covered.  One launch on the current stream; nothing synchronises."""
+    H, W = int(height), int(width)
+    if H < 1 or W < 1 or H * W >= GBUFFER_MAX_PIXELS:
+        raise RuntimeError(f'skeleton_panel: height = {H}, width = {W} must be positive with fewer than 2^31 pixels')
+    j = np.ascontiguousarray(np.asarray(joints))
+    if j.shape != (SKELETON_JOINTS, 3) or j.dtype != np.float32:
+        raise RuntimeError(f'skeleton_panel: joints must be float32 [{SKELETON_JOINTS},3], got {j.dtype} {j.shape}')
+    K = np.ascontiguousarray(np.asarray(K, dtype=np.float64)[:3, :3])
+    E = np.ascontiguousarray(np.asarray(E, dtype=np.float64))
+    if K.shape != (3, 3) or E.shape != (4, 4):
+        raise RuntimeError(f'skeleton_panel: K must be [3,3] and E [4,4], got {K.shape} and {E.shape}')
+    if K[0, 1] != 0.0:
+        raise NotImplementedError(f'skeleton_panel: skew K[0,1] = {K[0, 1]!r} is not built')
+    r = float(bone_px)
+    if not 0.0 <= r <= 1.0e6:
+        raise RuntimeError(f'skeleton_panel: bone_px = {bone_px!r} outside 0..1e6')
+    pal = np.ascontiguousarray(np.asarray(palette))
+    bg = np.ascontiguousarray(np.asarray(bgcolor_u8))
+    if pal.shape != (SKELETON_JOINTS, 3) or pal.dtype != np.uint8 or bg.shape != (3,) or bg.dtype != np.uint8:
+        raise RuntimeError(f'skeleton_panel: palette must be uint8 [{SKELETON_JOINTS},3] and bgcolor_u8 uint8 [3], got '
+                           f'{pal.dtype} {pal.shape} and {bg.dtype} {bg.shape}')
+    dev = torch.device(device)
+    blocks = int(_lib.lib().occnerf_skeleton_panel_blocks(H, W))
+    with _guard_dev(dev):
+        img = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+        record = torch.empty(1 + blocks, device=dev, dtype=torch.int32)
+        rc = _lib.lib().occnerf_skeleton_panel(j.ctypes.data, K.ctypes.data, E.ctypes.data, r, pal.ctypes.data, bg.ctypes.data,
+                                               H, W, img.data_ptr(), record.data_ptr(),
+                                               torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(rc, 'skeleton_panel')
+    return img, record

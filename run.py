@@ -1,6 +1,6 @@
 """Render entry point with the reference's command line (run.py:246-247, configs/config.py:65-72):
 
-    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,backview,movement,allview,evaluate,mesh} [KEY VALUE ...]
+    python run.py --cfg configs/occnerf/synthetic/occnerf.yaml --type {tpose,freeview,backview,movement,allview,evaluate,mesh,animate} [KEY VALUE ...]
 
 Frames go to experiments/<category>/<task>/<subject>/<experiment>/<load_net>/<folder>/NNNNNN.png
 exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seeded[:N]` renders the
@@ -9,6 +9,9 @@ seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on dis
 with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json (run_mesh below).
 `show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
 `geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
+`--type animate animate.motion PATH` drives the subject of a prepared dataset with a motion it has not seen (occnerf_amd/
+animate.py): frames to <...>/<load_net>/animate/NNNNNN.png, what was rendered to animate.json beside the folder; `show_skeleton
+True` puts the driving skeleton directly behind rgb (occnerf_amd/skeleton.py).
 
 Several GPUs: start it under torchrun, one process per GPU --
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 run.py --cfg ... --type movement
@@ -120,8 +123,19 @@ def _render(data_type, folder_name):
                        'depth_range': 'per frame: near.min() .. far.max()' if geo.get('depth_range') is None
                        else [float(v) for v in geo.depth_range],
                        'definition': 'DESIGN.md section 7k'}, f, indent=1)
+    # --type animate (occnerf_amd/animate.py): what was rendered goes to <folder>.json, and with
+    # show_skeleton the driving skeleton from the frame's own camera stands directly behind rgb -- one launch per frame here,
+    # on rank 0 after the gather.  No other type takes either branch
+    animate_log = [] if data_type == 'animate' and rank == 0 else None
+    show_skeleton = data_type == 'animate' and bool(cfg.get('show_skeleton'))
     torch.cuda.synchronize()
     t_wall0 = time.perf_counter()
+
+    def skeleton_of(meta):
+        from occnerf_amd.skeleton import skeleton_panel
+        v = meta if 'joints' in meta else loader.view(meta['idx'])         # the host route's meta carries no camera
+        return skeleton_panel(v['joints'], v['K'], v['E'], meta['height'], meta['width'], dev,
+                              bone_px=float(cfg.animate.get('bone_px', 3.0)), bgcolor=cfg.bgcolor)
 
     def on_frame(out, meta):                           # rank 0 only
         rgb_img, alpha_img = assemble_uint8_device(meta['width'], meta['height'], meta['ray_index'],
@@ -131,6 +145,11 @@ def _render(data_type, folder_name):
         # photograph as 8-bit pixels, where the loader has one (a prepared dataset; tpose has none)
         panels = [rgb_img] + ([meta['truth_u8']] if cfg.show_truth and 'truth_u8' in meta else []) + \
             ([alpha_img] if cfg.show_alpha else [])
+        if animate_log is not None:
+            animate_log.append(dict(loader.describe_frame(meta['idx']), rays=int(meta['ray_index'].numel())))
+            if show_skeleton:                              # [rgb, skeleton, alpha, ...]; its count record is read after the run
+                skeleton_img, animate_log[-1]['record'] = skeleton_of(meta)
+                panels.insert(1, skeleton_img)
         maps = None
         if geo_panels or geo_dir:
             # [rgb, truth, alpha, depth, normal, shaded]: two launches on what rank 0 holds after the gather; the depth range
@@ -144,7 +163,7 @@ def _render(data_type, folder_name):
         img_dev = torch.cat(panels, dim=1) if len(panels) > 1 else rgb_img
         # uint8 over PCIe into a pinned staging buffer; the writer thread waits for the copy and encodes the PNG
         # while the next frame renders (nothing here blocks on the GPU)
-        _, name = writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type in ('movement', 'backview') else None)
+        _, name = writer.append_device(img_dev, img_name=f"{meta['idx']:06d}" if data_type in ('movement', 'backview', 'animate') else None)
         if geo_dir:                                        # the raw maps, by the same writer thread and staging scheme
             writer.append_device_npz({k: maps[k] for k in ('t', 'normal', 'valid', 't_range')},
                                      os.path.join(geo_dir, f'{name}.npz'))
@@ -165,6 +184,14 @@ def _render(data_type, folder_name):
     torch.cuda.synchronize()
     t_render = time.perf_counter() - t_wall0
     writer.finalize()
+    if animate_log is not None:
+        from occnerf_amd.animate import write_json
+        from occnerf_amd.skeleton import counts
+        for entry in animate_log:
+            if 'record' in entry:
+                c = counts(entry.pop('record'))
+                entry.update(joints_dropped=c['dropped'], pixels_covered=c['covered'])
+        write_json(writer.image_dir + '.json', loader, animate_log)
     n_rays = stats['rays']
     print(f'{n_rays} rays in {t_render:.3f} s -> {n_rays / max(t_render, 1e-9):.0f} rays/s (frame generation and image '
           f'assembly included; PNG encoding runs beside it)')
@@ -197,6 +224,12 @@ def run_movement():
 def run_backview():
     """Every frame of the dataset from the camera behind the first frame's (core/data/occnerf/backview.py)."""
     _render('backview', 'backview' if not cfg.render_folder_name else cfg.render_folder_name)
+
+
+def run_animate():
+    """The subject of the movement source's prepared dataset driven by the motion animate.motion names (occnerf_amd/animate.py;
+    the reference has no such type): frames named by their index like movement's, animate.json beside the folder."""
+    _render('animate', 'animate' if not cfg.render_folder_name else cfg.render_folder_name)
 
 
 def run_allview():
@@ -308,5 +341,6 @@ def run_mesh():
 if __name__ == '__main__':
     fn = globals().get(f'run_{args.type}')
     if fn is None:
-        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, backview, movement, allview, evaluate, mesh")
+        raise SystemExit(f"--type {args.type}: supported are tpose, freeview, backview, movement, allview, evaluate, mesh, "
+                         'animate')
     fn()
