@@ -19,6 +19,7 @@ Per-frame small stuff (pose decoder, motion bases, motion-weight volume) stays t
 There is no CPU path: forward() raises if the parameters are not on a GPU.
 """
 import os
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -27,9 +28,20 @@ import torch.nn as nn
 from . import geometry, ops
 from .canonical_mlp import CanonicalMLP
 from .config import get_cfg
+from .packed import PackedMLPs
 from .rayorder import ray_patch_order
 from .modules import (BodyPoseRefiner, MotionBasisComputer, MotionWeightVolumeDecoder,
                       NonRigidMotionMLP, hann_window_weights)
+
+
+class KnnCenter(NamedTuple):
+    """A frame's collapse point (Network._knn_center).  center, idx: ops.knn_center's pair, what the kNN kernel's centre cache
+    takes.  row: ops.center_row of a sample at the centre (its cached feature row), stamp: what that row was computed from
+    (ops.sample_features' freshness contract) -- both None where only the neighbour lists are wanted (the training path)."""
+    center: torch.Tensor
+    idx: torch.Tensor
+    row: Optional[torch.Tensor] = None
+    stamp: Optional[tuple] = None
 
 
 class _Replica(nn.Module):
@@ -209,33 +221,12 @@ class Network(nn.Module):
 
     def _packed_weights(self):
         """MFMA-ordered MLP weights, repacked whenever a packed parameter changed (optimizer steps update
-        the tensors in place: their `_version` counters move, whatever mode the module is in)."""
-        cm, nr = self.cnl_mlp.module, self.non_rigid_mlp.module
-        nr_lin = [m for m in nr.block_mlps if isinstance(m, nn.Linear)]
-        cw, cb = cm.linear_params()
-        prec = str(self.cfg.get('mlp_precision', 'fp32'))
-        if prec not in ('fp32', 'bf16x3', 'f16x3'):
-            raise RuntimeError(f"cfg.mlp_precision must be 'fp32', 'f16x3' or 'bf16x3', got {prec!r}")
-        # the split-operand kernels take their weights as a second, 2-byte stream: bf16 pieces (bf16x3) or fp16 pieces with a
-        # scaled low part (f16x3, fp32-grade: csrc/split.h); the ops dispatch on that stream's dtype
-        pack_c = {'bf16x3': ops.canonical_mlp_pack_bf16, 'f16x3': ops.canonical_mlp_pack_f16}.get(prec)
-        pack_n = {'bf16x3': ops.nonrigid_pack_bf16, 'f16x3': ops.nonrigid_pack_f16}.get(prec)
-        srcs = cw + cb + [m.weight for m in nr_lin] + [m.bias for m in nr_lin]
-        key = (prec, str(self.cfg.get('f16x3_domain_check', True))) + tuple((t.data_ptr(), t._version) for t in srcs)
-        if self._packed is not None and self._packed['key'] == key:
-            return self._packed
-        self._packed = {
-            'key': key,
-            'cnl': ops.canonical_mlp_pack(cw, cb),
-            'cnl_bf16': pack_c(cw) if pack_c else None,
-            'nr': ops.nonrigid_pack([m.weight.detach() for m in nr_lin],
-                                    [m.bias.detach() for m in nr_lin]),
-            'nr_bf16': pack_n([m.weight.detach() for m in nr_lin]) if pack_n else None,
-            'nr_w0': nr_lin[0].weight.detach(), 'nr_b0': nr_lin[0].bias.detach(),
-            # f16x3: the word its kernels set when a hidden activation reaches the mode's clamp (4 094; csrc/split.h)
-            'domain_flag': torch.zeros(1, device=cw[0].device, dtype=torch.int32)
-            if (prec == 'f16x3' and self.cfg.get('f16x3_domain_check', True)) else None,
-        }
+        the tensors in place: their `_version` counters move, whatever mode the module is in), or cfg.mlp_precision or
+        cfg.f16x3_domain_check did: a PackedMLPs (occnerf_amd/packed.py), which also picks the kernels they go to."""
+        src = (self.cnl_mlp.module, self.non_rigid_mlp.module, str(self.cfg.get('mlp_precision', 'fp32')),
+               self.cfg.get('f16x3_domain_check', True))
+        if self._packed is None or self._packed.key != PackedMLPs.cache_key(*src):
+            self._packed = PackedMLPs(*src)
         return self._packed
 
     def _weight_constants(self):
@@ -280,32 +271,81 @@ class Network(nn.Module):
         return table
 
     # ------------------------------------------------------------------ sample pipeline
-    def _stage_features(self, rays8, z, xyz, mask, pk, cond, hann, table, pack, center=None):
-        """First half of a pass on the live-sample list (VALU / texture-path kernels + the non-rigid MLP): live list, non-rigid
-        offsets, repeated-sample heads, kNN, features.  -> state for `_stage_mlp_composite`.  List and count of the live samples
-        stay on the device: no host round trip in the frame."""
+    def _sample_features(self, xyz, knn, table, pack=None, **kw):
+        """ops.sample_features with the per-model arguments (points, normals, visibility counts, bound, hash grid) filled in."""
+        ctx, enc = self._context(), self.cnl_mlp.module.encoder
+        return ops.sample_features(
+            xyz, knn, self.point_base.detach(), ctx['normals'], ctx['unit'], self.point_counter.detach(), table,
+            ctx['bound32'], ctx['two_bound32'], enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale,
+            enc.base_resolution, pack=pack, **kw)
+
+    def _knn_center(self, cond, hann, table=None, pack=None):
+        """ops.knn_center's (center, idx) for this frame's collapse point: wherever a sample's motion-weight sum is far below
+        the 1e-4 clamp of the reference's warp (network.py:388) its warped position lands within a micrometre of the origin,
+        hence -- after the non-rigid offset -- of offset(0): two thirds of a frame's live samples.  The kNN kernel hands those
+        queries c's neighbour lists when they lie inside the radius in which the lists provably hold (exact: DESIGN.md 3.2).
+        With the frame's table (and point pack) the record also carries c's feature row and what it was computed from."""
+        ctx, pk = self._context(), self._packed_weights()
+        c = torch.zeros(64, 3, device=self.point_base.device)
+        if not self.cfg.ignore_non_rigid_motions:
+            # (any point near the cluster serves as c -- the radius is proven for whatever c is searched -- so the first-version
+            # kernel's offset(0), equal to the LDS-staged kernel's to fp32 rounding, does; it keeps the per-kernel profiles of the
+            # frame's one big nr16 launch clean)
+            c = ops.nonrigid(c, cond, hann, pk.nr_w0, pk.nr_b0, pk.nr, direct=True)
+        center, idx = ops.knn_center(c[0].contiguous(), ctx['points'], ctx['index_map'], ctx['scale_begin'])
+        if table is None:
+            return KnnCenter(center, idx)
+        # ... and the 36 leading feature columns every sample with c's neighbour lists has (functions of the 40 ids, the
+        # visibility counts and the per-point table alone): the feature kernel on samples at c
+        row, _, enc_in = self._sample_features(c[:8].contiguous(), idx[None].expand(8, -1, -1).contiguous(), table, pack,
+                                               want_enc_in=True)
+        return KnnCenter(center, idx, ops.center_row(row[0], enc_in[0]), self._center_stamp(table))
+
+    @staticmethod
+    def _put_center_row(mlp_in, at, row):
+        """Row `at` of a canonical-MLP input buffer from a KnnCenter.row: ops.center_row's 36 | 4 | 32 layout without the four
+        encoder inputs in its middle."""
+        mlp_in[at, :36] = row[:36]
+        mlp_in[at, 36:] = row[40:72]
+
+    def _center_stamp(self, table):
+        return (table.data_ptr(), table._version, self.point_counter._version, self.cnl_mlp.module.encoder.embeddings._version)
+
+    def _render_rays(self, pk, rays8, Rs, Ts, vol, bbox_min, bbox_scale, bgcolor, cond, hann,
+                     table, t_rand=None, out=None, out_rows=None, pack=None, boxes=None, center=None):
+        """One pass: sample and warp, non-rigid offsets, repeated-sample heads / centre split, kNN, features, canonical MLP,
+        results back to their samples, alpha compositing.  pk: the frame's PackedMLPs; center: its KnnCenter or None.
+        out: (rgb[R,3], alpha[R], depth[R]) of the whole frame; this pass's rays land in rows out_rows (their index
+        in the caller's order) or, without a permutation, in the slice the caller passes."""
         cfg, ctx = self.cfg, self._context()
         S = int(cfg.N_samples)
-        enc = self.cnl_mlp.module.encoder
-        rows, count = ops.live_rows(mask)
-        self.last_live_count = count
-        dedup = bool(cfg.get('dedup_repeated_samples', True))
+        t_vals = torch.linspace(0., 1., steps=S, device=rays8.device)
+        z, xyz, mask, _ = ops.sample_warp(rays8, S, t_vals, Rs, Ts, vol, bbox_min, bbox_scale,
+                                          t_rand=t_rand, boxes=boxes)
+        N, dev = xyz.shape[0], xyz.device
+        culling = bool(cfg.get('knn_culling', True))
+        # Samples whose motion-weight sum is exactly 0 (outside every bone's prior support or outside the
+        # canonical volume) cannot contribute: their alpha is multiplied by that sum (network.py:330).  They
+        # are dropped here -- a quarter of the samples of the benchmark frame -- and the pixel values are
+        # bit-identical to evaluating them (cfg.skip_empty_samples=False; tested).
+        # (fp32 and the opt-in split-operand kernels alike: list and count of the live samples stay on the device, no host round
+        # trip in the frame.  rows is None: every sample evaluated, cfg.skip_empty_samples off and / or the brute-force
+        # neighbour search, cfg.knn_culling off.)
+        rows = count = None
+        if cfg.get('skip_empty_samples', True) and culling:
+            rows, count = ops.live_rows(mask)
+            self.last_live_count = count
+        if not cfg.ignore_non_rigid_motions:
+            pk.offsets(xyz, cond, hann, rows=rows, count=count, out=xyz)
         # Repeated samples (ops.repeat_heads): consecutive live samples with a bitwise identical canonical position
         # share the neighbour search and the features, consecutive feature rows that are bitwise identical share the
         # MLP result.
         # Each distinct input is evaluated once and every sample receives its head's result: bit-identical pixels
         # (cfg.dedup_repeated_samples=False evaluates every live sample; tested).
-        scan_a = scan_b = mrows = mcount = None
-        frows, fcount, kmask = rows, count, mask
-        if not cfg.ignore_non_rigid_motions:
-            if pk['nr_bf16'] is not None:      # opt-in split-bf16 MFMA path (cfg.mlp_precision): same list, same count
-                ops.nonrigid_bf16x3_rows(xyz, rows, count, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], pk['nr_bf16'],
-                                         domain_flag=pk['domain_flag'])
-            else:
-                ops.nonrigid_rows(xyz, rows, count, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'])
+        dedup = rows is not None and bool(cfg.get('dedup_repeated_samples', True))
+        frows, fcount = rows, count             # the list the kNN and feature kernels run on
         if dedup:       # (the positions before the offset differ in their last bits; after it they coincide)
-            scan_a, frows, fcount, kmask = ops.repeat_heads(xyz, 3, count, rows=rows,
-                                                            want_mask=not cfg.get('knn_query_list', True))
+            scan_a, frows, fcount, _ = ops.repeat_heads(xyz, 3, count, rows=rows)
             # (the positions' repeats that are not neighbours in the list are few -- 9.28 M -> 8.39 M on the benchmark
             # frame -- and finding them, 1.7 ms, costs more than the kNN + feature work they save, 0.6 ms)
             if cfg.get('dedup_global_positions', False):
@@ -319,158 +359,55 @@ class Network(nn.Module):
         # the offsets come from the fp32 kernel the centre itself went through (or there are none).  The split-operand non-rigid
         # kernels round differently: the collapsed samples then sit a few 1e-7 m off c, their signed distance differs from c's
         # in its last bits, few are flagged and the stage costs more than it saves (profiles/r09_center_split.md).
-        split = None
-        self.last_center_taken = None
+        keep = raw_taken = mlp_buf = None
+        in_rows, ecount = None, count           # what the canonical MLP evaluates: every listed sample, from its own row
         want = cfg.get('center_split', 'auto')
         if want == 'auto':
-            want = pk['nr_bf16'] is None or bool(cfg.ignore_non_rigid_motions)
-        if not dedup and center is not None and len(center) > 2 and pack is not None and want and cfg.get('knn_query_list', True):
-            M = rows.shape[0]
-            raw_c = torch.empty(M, 5, device=xyz.device)
-            flag = ops.center_classify(xyz, rows, count, pack[0], center[0], center[1], center[2], ctx['bound32'],
-                                       ctx['two_bound32'], raw_c)
-            keep, frows, fcount, in_rows, taken = ops.center_split(flag, rows, count, M)
-            mlp_buf = torch.empty(M + 1, 68, device=xyz.device)
-            mlp_buf[M, :36] = center[2][:36]            # the layout of ops.center_row without the encoder input
-            mlp_buf[M, 36:] = center[2][40:72]
-            split = {'keep': keep, 'count2': fcount, 'in_rows': in_rows, 'raw_c': raw_c, 'mlp_buf': mlp_buf}
-            self.last_center_taken = taken
-        self.last_head_counts = (fcount, None)
-        if cfg.get('knn_query_list', True):    # tiles formed over the listed samples only (same indices, tested)
+            want = pk.nr_split is None or bool(cfg.ignore_non_rigid_motions)
+        if rows is not None:
+            self.last_center_taken = None
+            if not dedup and center is not None and center.row is not None and pack is not None and want:
+                M = rows.shape[0]
+                raw_taken = torch.empty(M, 5, device=dev)
+                flag = ops.center_classify(xyz, rows, count, pack[0], center.center, center.idx, center.row, ctx['bound32'],
+                                           ctx['two_bound32'], raw_taken)
+                keep, frows, fcount, in_rows, self.last_center_taken = ops.center_split(flag, rows, count, M)
+                mlp_buf = torch.empty(M + 1, 68, device=dev)
+                self._put_center_row(mlp_buf, M, center.row)
+            self.last_head_counts = (fcount, None)
+        # (the clustered search: the brute-force one's results with ~5x fewer distance evaluations; its tiles are formed over the
+        # listed samples only -- same indices, tested)
+        if culling:
             knn = ops.msknn_clustered(xyz, rays8.shape[0], S, ctx['clusters'], ctx['seed'], rows=frows, count=fcount, center=center)
         else:
-            knn = ops.msknn_clustered(xyz, rays8.shape[0], S, ctx['clusters'], ctx['seed'], mask=kmask, center=center)
-        if center is not None and len(center) > 3 and center[3] != self._center_stamp(table):
+            knn = ops.msknn(xyz, ctx['points'], ctx['index_map'], ctx['scale_begin'], ctx['seed'])
+        # (the feature kernel takes the centre's row on the listed-sample path only, as it always has)
+        fcenter = center if rows is not None else None
+        if fcenter is not None and fcenter.stamp is not None and fcenter.stamp != self._center_stamp(table):
             raise RuntimeError('stale kNN centre: its cached feature row was computed from another table / counter / embedding '
                                'version than this frame\'s (ops.sample_features freshness contract)')
-        mlp_in, raw_c, _ = ops.sample_features(
-            xyz, knn, self.point_base.detach(), ctx['normals'], ctx['unit'],
-            self.point_counter.detach(), table, ctx['bound32'], ctx['two_bound32'],
-            enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale, enc.base_resolution,
-            rows=frows, count=fcount, pack=pack, center=None if center is None else center[0],
-            center_agg=None if center is None else center[2], mlp_in_out=None if split is None else split['mlp_buf'])
+        mlp_in, raw_c, _ = self._sample_features(
+            xyz, knn, table, pack, rows=frows, count=fcount, center=None if fcenter is None else fcenter.center,
+            center_agg=None if fcenter is None else fcenter.row, mlp_in_out=mlp_buf)
         del knn
-        in_rows = None
-        if split is not None:       # the kept entries' distance joins the flagged ones': raw_c is complete, in list order
-            raw_c = ops.center_merge_dist(raw_c, split['keep'], split['count2'], split['raw_c'])
-            in_rows = split['in_rows']
+        if keep is not None:        # the kept entries' distance joins the flagged ones': raw_c is complete, in list order
+            raw_c = ops.center_merge_dist(raw_c, keep, fcount, raw_taken)
         if dedup:
-            scan_b, mrows, mcount, _ = ops.repeat_heads(mlp_in, 68, fcount)
+            scan_b, in_rows, ecount, _ = ops.repeat_heads(mlp_in, 68, fcount)
             if cfg.get('dedup_global', True):       # ... and the repeats that are not neighbours in the list
-                mrows, mcount = ops.unique_heads(mlp_in, 68, mrows, mcount, scan=scan_b, scan_count=fcount)
-            self.last_head_counts = (fcount, mcount)
-        return {'dedup': dedup, 'rays8': rays8, 'z': z, 'mask': mask, 'rows': rows, 'count': count, 'mlp_in': mlp_in,
-                'raw_c': raw_c, 'in_rows': in_rows, 'scan_a': scan_a, 'scan_b': scan_b, 'mrows': mrows, 'mcount': mcount, 'cnl': pk['cnl'],
-                'cnl_bf16': pk['cnl_bf16'], 'domain_flag': pk['domain_flag'], 'N': xyz.shape[0]}
-
-    @staticmethod
-    def _stage_mlp_composite(st, bgcolor, out, out_rows):
-        """Second half of a pass (the matrix-pipe kernel + the per-ray scan): canonical MLP on the feature rows, results back
-        to their samples, alpha compositing into the frame's rows."""
-        dev, N = st['mlp_in'].device, st['N']
-
-        def mlp(raw_out, count, in_rows=None):
-            if st['cnl_bf16'] is not None:          # opt-in split-bf16 MFMA path (cfg.mlp_precision)
-                ops.canonical_mlp_bf16x3(st['mlp_in'], st['cnl'], st['cnl_bf16'], raw_out, count=count, in_rows=in_rows,
-                                         domain_flag=st['domain_flag'])
-            else:
-                ops.canonical_mlp(st['mlp_in'], st['cnl'], raw_out, count=count, in_rows=in_rows)
-        if st['dedup']:
-            raw_h = torch.empty(st['mlp_in'].shape[0], 5, device=dev)
-            mlp(raw_h, st['mcount'], st['mrows'])
-            raw = ops.scatter_raw_heads(raw_h, st['raw_c'], st['rows'], st['count'], st['scan_a'], st['scan_b'],
-                                        torch.zeros(N, 5, device=dev))
-        else:
-            mlp(st['raw_c'], st['count'], st['in_rows'])      # (in_rows: the centre split's; None without it)
-            raw = ops.scatter_raw(st['raw_c'], st['rows'], st['count'], torch.zeros(N, 5, device=dev))
-        st['mlp_in'] = None
-        return ops.composite(raw, st['mask'], st['z'], st['rays8'], bgcolor, out=out, out_rows=out_rows)[:3]
-
-    def _nonrigid_f16_pack(self):
-        """Split-fp16 operand stream of the non-rigid MLP for the bf16 training step (kept beside the fp32 pack, same key)."""
-        pk = self._packed_weights()
-        if pk.get('nr_f16_train') is None:
-            nr_lin = [m for m in self.non_rigid_mlp.module.block_mlps if isinstance(m, nn.Linear)]
-            pk['nr_f16_train'] = pk['nr_bf16'] if (pk['nr_bf16'] is not None and pk['nr_bf16'].dtype == torch.float16) else \
-                ops.nonrigid_pack_f16([m.weight.detach() for m in nr_lin])
-        return pk['nr_f16_train']
-
-    def _knn_center_lists(self, cond, hann):
-        """(center[4], idx[4,10]) of ops.knn_center at this frame's collapse point (see _knn_center): what the kNN kernel's
-        centre cache takes -- without the cached feature row the renderer adds."""
-        ctx, pk = self._context(), self._packed_weights()
-        c = torch.zeros(64, 3, device=self.point_base.device)
-        if not self.cfg.ignore_non_rigid_motions:
-            c = ops.nonrigid(c, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], direct=True)
-        return ops.knn_center(c[0].contiguous(), ctx['points'], ctx['index_map'], ctx['scale_begin'])
-
-    def _knn_center(self, cond, hann, table, pack):
-        """(center, idx) of ops.knn_center for this frame's collapse point: wherever a sample's motion-weight sum is far below
-        the 1e-4 clamp of the reference's warp (network.py:388) its warped position lands within a micrometre of the origin,
-        hence -- after the non-rigid offset -- of offset(0): two thirds of a frame's live samples.  The kNN kernel hands those
-        queries c's neighbour lists when they lie inside the radius in which the lists provably hold (exact: DESIGN.md 3.2)."""
-        ctx, pk = self._context(), self._packed_weights()
-        c = torch.zeros(64, 3, device=self.point_base.device)
-        if not self.cfg.ignore_non_rigid_motions:
-            # (any point near the cluster serves as c -- the radius is proven for whatever c is searched -- so the first-version
-            # kernel's offset(0), equal to the LDS-staged kernel's to fp32 rounding, does; it keeps the per-kernel profiles of the
-            # frame's one big nr16 launch clean)
-            c = ops.nonrigid(c, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], direct=True)
-        center, idx = ops.knn_center(c[0].contiguous(), ctx['points'], ctx['index_map'], ctx['scale_begin'])
-        # ... and the 36 leading feature columns every sample with c's neighbour lists has (functions of the 40 ids, the
-        # visibility counts and the per-point table alone): the feature kernel on samples at c
-        enc = self.cnl_mlp.module.encoder
-        row, _, enc_in = ops.sample_features(
-            c[:8].contiguous(), idx[None].expand(8, -1, -1).contiguous(), self.point_base.detach(), ctx['normals'], ctx['unit'],
-            self.point_counter.detach(), table, ctx['bound32'], ctx['two_bound32'], enc.embeddings.detach(), enc.offsets,
-            enc.log2_per_level_scale, enc.base_resolution, pack=pack, want_enc_in=True)
-        # (the 4th entry pins what the cached row was computed from: ops.sample_features' freshness contract)
-        return center, idx, ops.center_row(row[0], enc_in[0]), self._center_stamp(table)
-
-    def _center_stamp(self, table):
-        return (table.data_ptr(), table._version, self.point_counter._version, self.cnl_mlp.module.encoder.embeddings._version)
-
-    def _render_rays(self, rays8, Rs, Ts, vol, bbox_min, bbox_scale, bgcolor, cond, hann,
-                     table, t_rand=None, out=None, out_rows=None, pack=None, boxes=None, center=None):
-        """out: (rgb[R,3], alpha[R], depth[R]) of the whole frame; this pass's rays land in rows out_rows (their index
-        in the caller's order) or, without a permutation, in the slice the caller passes."""
-        cfg, ctx = self.cfg, self._context()
-        S = int(cfg.N_samples)
-        enc = self.cnl_mlp.module.encoder
-        t_vals = torch.linspace(0., 1., steps=S, device=rays8.device)
-        z, xyz, mask, _ = ops.sample_warp(rays8, S, t_vals, Rs, Ts, vol, bbox_min, bbox_scale,
-                                          t_rand=t_rand, boxes=boxes)
-        pk = self._packed_weights()
-        # Samples whose motion-weight sum is exactly 0 (outside every bone's prior support or outside the
-        # canonical volume) cannot contribute: their alpha is multiplied by that sum (network.py:330).  They
-        # are dropped here -- a quarter of the samples of the benchmark frame -- and the pixel values are
-        # bit-identical to evaluating them (cfg.skip_empty_samples=False; tested).
-        N = xyz.shape[0]
-        if cfg.get('skip_empty_samples', True) and cfg.get('knn_culling', True):
-            # (fp32 and the opt-in split-bf16 kernels alike: list and count of the live samples on the device, no host sync)
-            st = self._stage_features(rays8, z, xyz, mask, pk, cond, hann, table, pack, center)
-            return self._stage_mlp_composite(st, bgcolor, out, out_rows)
-
-        # every sample evaluated (cfg.skip_empty_samples off) and / or the brute-force neighbour search (cfg.knn_culling off)
-        if not cfg.ignore_non_rigid_motions:
-            if pk['nr_bf16'] is not None:
-                ops.nonrigid_bf16x3(xyz, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], pk['nr_bf16'], out=xyz, domain_flag=pk['domain_flag'])
-            else:
-                ops.nonrigid(xyz, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], out=xyz)
-        if cfg.get('knn_culling', True):     # same results, ~5x fewer distance evaluations
-            knn = ops.msknn_clustered(xyz, rays8.shape[0], S, ctx['clusters'], ctx['seed'], center=center)
-        else:
-            knn = ops.msknn(xyz, ctx['points'], ctx['index_map'], ctx['scale_begin'], ctx['seed'])
-        mlp_in, raw, _ = ops.sample_features(
-            xyz, knn, self.point_base.detach(), ctx['normals'], ctx['unit'],
-            self.point_counter.detach(), table, ctx['bound32'], ctx['two_bound32'],
-            enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale, enc.base_resolution, pack=pack)
-        del knn
-        if pk['cnl_bf16'] is not None:          # opt-in split-bf16 MFMA path (cfg.mlp_precision)
-            ops.canonical_mlp_bf16x3(mlp_in, pk['cnl'], pk['cnl_bf16'], raw, domain_flag=pk['domain_flag'])
-        else:
-            ops.canonical_mlp(mlp_in, pk['cnl'], raw)
+                in_rows, ecount = ops.unique_heads(mlp_in, 68, in_rows, ecount, scan=scan_b, scan_count=fcount)
+            self.last_head_counts = (fcount, ecount)
+        # the matrix-pipe kernel (in_rows: the heads' or the centre split's; None without either), its results back to their
+        # samples, and the per-ray scan
+        raw_e = torch.empty(mlp_in.shape[0], 5, device=dev) if dedup else raw_c
+        pk.canonical(mlp_in, raw_e, count=ecount, in_rows=in_rows)
         del mlp_in
+        if dedup:
+            raw = ops.scatter_raw_heads(raw_e, raw_c, rows, count, scan_a, scan_b, torch.zeros(N, 5, device=dev))
+        elif rows is not None:
+            raw = ops.scatter_raw(raw_c, rows, count, torch.zeros(N, 5, device=dev))
+        else:
+            raw = raw_c
         return ops.composite(raw, mask, z, rays8, bgcolor, out=out, out_rows=out_rows)[:3]
 
     @staticmethod
@@ -492,20 +429,27 @@ class Network(nn.Module):
         host round trip): the per-frame preamble and the sampler/warp kernel only -- what a frame costs per ray, since
         every later stage runs on the live samples.  occnerf_amd/parallel.py probes a sixteenth of a frame's rays with it
         to deal rays to GPUs by cost."""
-        cfg, dev = self.cfg, self.point_base.device
+        dev = self.point_base.device
         f32 = lambda t: t.detach().float().contiguous().to(dev)          # noqa: E731
-        wc = self._weight_constants()
-        refine = iter_val >= cfg.pose_decoder.get('kick_in_iter', 0)
-        Rs, Ts = ops.pose_motion_bases(self.pose_decoder, f32(dst_posevec).reshape(-1), refine, f32(dst_Rs), f32(dst_Ts),
-                                       f32(cnl_gtfms))
-        vol = ops.prior_softmax(wc['dec'], f32(motion_weights_priors))
+        Rs, Ts, vol, boxes = self.render_preamble(
+            dict(dst_posevec=dst_posevec, dst_Rs=dst_Rs, dst_Ts=dst_Ts, cnl_gtfms=cnl_gtfms,
+                 motion_weights_priors=motion_weights_priors), iter_val, boxes=True)
         rays8 = ops.pack_rays(f32(rays).reshape(2, -1, 3), f32(near).reshape(-1), f32(far).reshape(-1), None)
-        S = int(cfg.N_samples)
+        S = int(self.cfg.N_samples)
         t_vals = torch.linspace(0., 1., steps=S, device=dev)
-        boxes = ops.bone_boxes(vol, Rs.shape[0]) if cfg.get('warp_bone_culling', True) else None
         _, _, mask, _ = ops.sample_warp(rays8, S, t_vals, Rs, Ts, vol, self._host3(kwargs['cnl_bbox_min_xyz']),
                                         self._host3(kwargs['cnl_bbox_scale_xyz']), boxes=boxes)
         return (mask.view(-1, S) != 0).sum(dim=1)
+
+    def _require_points(self, name, t):
+        """The public point queries take float32 [N,3] on the module's device; name: '<method>: <argument>'.  (Called through
+        the class: a host tensor is refused before `self` is looked at -- the wrapper tests pass None for it.)"""
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError(f'{name} must be a CUDA(HIP) tensor; there is no CPU path')
+        if t.dim() != 2 or t.shape[1] != 3 or t.dtype != torch.float32:
+            raise RuntimeError(f'{name} must be float32 [N,3], got {t.dtype} {tuple(t.shape)}')
+        if t.device != self.point_base.device:
+            raise RuntimeError(f'{name} is on {t.device}, the module on {self.point_base.device}')
 
     @torch.no_grad()
     def query_canonical(self, xyz, chunk=1 << 21):
@@ -518,12 +462,7 @@ class Network(nn.Module):
         chunk padded to a multiple of 128 by repeating its last point, the padding dropped); every row is a function of its
         own point alone, so the result does not depend on `chunk` bit for bit.  Nothing of the module changes: not its
         train / eval mode, `point_counter`, the renderer's caches or any RNG state."""
-        if not torch.is_tensor(xyz) or not xyz.is_cuda:
-            raise RuntimeError('query_canonical: xyz must be a CUDA(HIP) tensor; there is no CPU path')
-        if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.dtype != torch.float32:
-            raise RuntimeError(f'query_canonical: xyz must be float32 [N,3], got {xyz.dtype} {tuple(xyz.shape)}')
-        if xyz.device != self.point_base.device:
-            raise RuntimeError(f'query_canonical: xyz is on {xyz.device}, the module on {self.point_base.device}')
+        Network._require_points(self, 'query_canonical: xyz', xyz)
         chunk = int(chunk)
         if chunk <= 0:
             raise RuntimeError(f'query_canonical: chunk = {chunk} must be positive')
@@ -534,10 +473,8 @@ class Network(nn.Module):
         if N == 0:
             return raw
         ctx = self._context()
-        enc = self.cnl_mlp.module.encoder
         table = self._point_stage(ctx)                 # (this call's own: the renderer's cached constants are left alone)
-        base, counter = self.point_base.detach(), self.point_counter.detach()
-        pack = ops.point_pack(base, ctx['normals'], ctx['unit'], counter, table)
+        pack = ops.point_pack(self.point_base.detach(), ctx['normals'], ctx['unit'], self.point_counter.detach(), table)
         cw, cb = self.cnl_mlp.module.linear_params()
         packed = ops.canonical_mlp_pack(cw, cb)
         xyz = xyz.detach().contiguous()
@@ -548,9 +485,7 @@ class Network(nn.Module):
             if pad:
                 x = torch.cat([x, x[-1:].expand(pad, 3)]).contiguous()
             knn = ops.msknn_clustered(x, (n + pad) // S, S, ctx['clusters'], ctx['seed'])
-            mlp_in, raw_c, _ = ops.sample_features(
-                x, knn, base, ctx['normals'], ctx['unit'], counter, table, ctx['bound32'], ctx['two_bound32'],
-                enc.embeddings.detach(), enc.offsets, enc.log2_per_level_scale, enc.base_resolution, pack=pack)
+            mlp_in, raw_c, _ = self._sample_features(x, knn, table, pack)
             del knn
             ops.canonical_mlp(mlp_in, packed, raw_c)
             raw[i:i + n] = raw_c[:n]
@@ -565,12 +500,7 @@ class Network(nn.Module):
         (ops.nonrigid_rows) with the frame's condition vector and Hann window formed exactly as the render forms them, whatever
         cfg.mlp_precision says.  With cfg.ignore_non_rigid_motions the render applies no offset: s = x_c bit for bit.
         One host wait per round.  Like query_canonical it changes nothing about the module (it packs its own weights)."""
-        if not torch.is_tensor(x_c) or not x_c.is_cuda:
-            raise RuntimeError('unoffset_canonical: x_c must be a CUDA(HIP) tensor; there is no CPU path')
-        if x_c.dim() != 2 or x_c.shape[1] != 3 or x_c.dtype != torch.float32:
-            raise RuntimeError(f'unoffset_canonical: x_c must be float32 [N,3], got {x_c.dtype} {tuple(x_c.shape)}')
-        if x_c.device != self.point_base.device:
-            raise RuntimeError(f'unoffset_canonical: x_c is on {x_c.device}, the module on {self.point_base.device}')
+        Network._require_points(self, 'unoffset_canonical: x_c', x_c)
         cfg, dev, N = self.cfg, x_c.device, x_c.shape[0]
         x_c = x_c.detach().contiguous()
         moving = torch.zeros(N, device=dev, dtype=torch.bool)
@@ -596,15 +526,21 @@ class Network(nn.Module):
         return s, moving
 
     @torch.no_grad()
-    def render_preamble(self, data, iter_val=1e7):
-        """(Rs[24,3,3], Ts[24,3], vol[25,G,G,G]) of a frame exactly as the render branch of `forward` computes them (the fused
-        kernels of csrc/preamble.hip) -- for parity tools that feed a checker the same per-frame outputs."""
+    def render_preamble(self, data, iter_val=1e7, boxes=False):
+        """(Rs[24,3,3], Ts[24,3], vol[25,G,G,G]) of a frame (the fused kernels of csrc/preamble.hip): what the render branch of
+        `forward` and `live_samples_per_ray` run on -- and parity tools that feed a checker the same per-frame outputs.
+        boxes=True: a fourth entry, what ops.sample_warp takes as `boxes`."""
         f32 = lambda t: t.detach().float().contiguous().to(self.point_base.device)          # noqa: E731
         wc = self._weight_constants()
         refine = iter_val >= self.cfg.pose_decoder.get('kick_in_iter', 0)
         Rs, Ts = ops.pose_motion_bases(self.pose_decoder, f32(data['dst_posevec']).reshape(-1), refine, f32(data['dst_Rs']),
                                        f32(data['dst_Ts']), f32(data['cnl_gtfms']))
-        return Rs, Ts, ops.prior_softmax(wc['dec'], f32(data['motion_weights_priors']))
+        vol = ops.prior_softmax(wc['dec'], f32(data['motion_weights_priors']))
+        if not boxes:
+            return Rs, Ts, vol
+        # support box of every bone's weight channel (one tiny launch): the warp kernel skips the bones that cannot
+        # reach a wave's samples -- same bits (cfg.warp_bone_culling=False: every bone for every sample)
+        return Rs, Ts, vol, (ops.bone_boxes(vol, Rs.shape[0]) if self.cfg.get('warp_bone_culling', True) else None)
 
     def forward(self, rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec=None,
                 near=None, far=None, iter_val=1e7, **kwargs):
@@ -613,9 +549,6 @@ class Network(nn.Module):
         if dev.type != 'cuda':
             raise RuntimeError('occnerf_amd.Network renders on a GPU only; move the module with '
                                '.cuda() first (the reference has no CPU path either)')
-        dst_Rs, dst_Ts = dst_Rs[None], dst_Ts[None]
-        dst_posevec, cnl_gtfms = dst_posevec[None], cnl_gtfms[None]
-        motion_weights_priors = motion_weights_priors[None]
         want_grad = torch.is_grad_enabled()
         # fused HIP render when no graph is wanted and the module is in eval mode; the staged differentiable
         # path otherwise (training mode under no_grad still produces comp_loss and the counter update, as the
@@ -663,6 +596,7 @@ class Network(nn.Module):
                 f32 = lambda t: t.detach().float().contiguous()          # noqa: E731
                 cond = f32(dst_posevec).reshape(-1) if iter_val >= nr.kick_in_iter else \
                     torch.zeros(dst_posevec.numel(), device=dev)
+                pk = self._packed_weights()      # the frame's MLP weights and kernels: taken once, handed down
                 # The collapse point's chain (its non-rigid offset, its neighbour lists and radius, its feature row: three
                 # single-workgroup kernels) runs on the caller's stream like everything else.  (Round 5 carried an opt-in
                 # side-stream placement and a two-stream chunk pipeline; both measured neutral to negative and were removed in
@@ -670,12 +604,9 @@ class Network(nn.Module):
                 center = None
                 if cfg.get('knn_center_cache', True) and cfg.get('knn_culling', True):
                     center = self._knn_center(cond, hann.tolist(), wc['table'], pack)
-                Rs, Ts = ops.pose_motion_bases(self.pose_decoder, f32(dst_posevec).reshape(-1), refine, f32(dst_Rs[0]),
-                                               f32(dst_Ts[0]), f32(cnl_gtfms[0]))
-                vol = ops.prior_softmax(wc['dec'], f32(motion_weights_priors[0]))
-                # support box of every bone's weight channel (one tiny launch): the warp kernel skips the bones that cannot
-                # reach a wave's samples -- same bits (cfg.warp_bone_culling=False: every bone for every sample)
-                boxes = ops.bone_boxes(vol, Rs.shape[0]) if cfg.get('warp_bone_culling', True) else None
+                Rs, Ts, vol, boxes = self.render_preamble(
+                    dict(dst_posevec=dst_posevec, dst_Rs=dst_Rs, dst_Ts=dst_Ts, cnl_gtfms=cnl_gtfms,
+                         motion_weights_priors=motion_weights_priors), iter_val, boxes=True)
                 rays_f = f32(torch.stack([rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)]) if not torch.is_tensor(rays) else
                              rays.reshape(2, -1, 3))
                 order = morton_order(rays_f[1])
@@ -691,24 +622,23 @@ class Network(nn.Module):
                     cap = min(cap, max(1 << 22, int(free // 2 // 470)))
                 rays_per_pass = max(1, cap // S)
 
-                def passes():
+                def passes(pk):
                     for i in range(0, R, rays_per_pass):
                         n = min(rays_per_pass, R - i)
-                        if order is not None:
-                            self._render_rays(rays8[i:i + n], Rs, Ts, vol, bbox_min, bbox_scale, bgcolor, cond, hann.tolist(),
-                                              wc['table'], out=out, out_rows=order[i:i + n], pack=pack, boxes=boxes, center=center)
-                        else:
-                            self._render_rays(rays8[i:i + n], Rs, Ts, vol, bbox_min, bbox_scale, bgcolor, cond, hann.tolist(),
-                                              wc['table'], out=tuple(t[i:i + n] for t in out), pack=pack, boxes=boxes, center=center)
-                passes()
+                        dst = {'out': out, 'out_rows': order[i:i + n]} if order is not None else \
+                            {'out': tuple(t[i:i + n] for t in out)}
+                        self._render_rays(pk, rays8[i:i + n], Rs, Ts, vol, bbox_min, bbox_scale, bgcolor, cond, hann.tolist(),
+                                          wc['table'], pack=pack, boxes=boxes, center=center, **dst)
+                passes(pk)
                 # f16x3 is exact-grade only inside its domain (hidden activations below 4 094: csrc/split.h); its kernels report
                 # leaving it -- never silently wrong pixels.  cfg.f16x3_domain_check: True / 'sync' (default) reads the flag after
-                # the frame (the read waits for the frame) and renders the frame AGAIN with the fp32 kernels when it is set;
+                # the frame (the read waits for the frame) and renders the frame AGAIN with the fp32 kernels when it is set (on the
+                # same packed weights' fp32 view: nothing is packed again, cfg is not touched);
                 # 'deferred' copies the flag to pinned memory behind the frame and looks at it when a later frame starts (or in
                 # check_f16x3_domain()): no wait in a pipelined loop, and a violation RAISES there, naming the frame, because
                 # that frame's pixels have already been handed out; False skips the check and the guarantee.
                 mode = cfg.get('f16x3_domain_check', True)
-                flag = self._packed_weights().get('domain_flag') if (R > 0 and mode) else None
+                flag = pk.domain_flag if (R > 0 and mode) else None
                 if flag is not None and mode == 'deferred':
                     self._f16x3_enqueue_check(flag, 'frame')
                 elif flag is not None and int(flag.item()) != 0:
@@ -718,18 +648,16 @@ class Network(nn.Module):
                         import warnings
                         warnings.warn("occnerf_amd: a hidden activation left the domain of cfg.mlp_precision='f16x3' (>= 4 094); "
                                       'this frame -- and every later one that does -- is rendered again with the fp32 kernels')
-                    prec0 = cfg.mlp_precision
-                    cfg.mlp_precision = 'fp32'
-                    try:
-                        passes()
-                    finally:
-                        cfg.mlp_precision = prec0
+                    passes(pk.exact())
                 rgb, acc, depth = out
                 comp_loss = torch.zeros(1, device=dev)
         else:
             # ---- differentiable path: per-frame modules in torch (gradients to the pose refiner and the volume
             # decoder), then HIP forward + HIP backward per stage (train_path.py) ----
             from . import train_path
+            dst_Rs, dst_Ts = dst_Rs[None], dst_Ts[None]
+            dst_posevec, cnl_gtfms = dst_posevec[None], cnl_gtfms[None]
+            motion_weights_priors = motion_weights_priors[None]
             self.check_f16x3_domain(wait=False)      # (the bf16 step's f16x3 offsets: flags of earlier steps that have arrived)
             with torch.set_grad_enabled(want_grad):
                 # the per-frame modules always run in fp32 (bone transforms in bf16 would move every sample); a caller's

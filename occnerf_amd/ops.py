@@ -651,7 +651,7 @@ def sample_features(xyz, knn_idxs, point_base, normals, unit, counter, table, bo
     `center` must come from ops.knn_center on the SAME point set the kNN indices were searched in, and `center_agg` from this
     function on a sample at that centre with the SAME table, counter, embeddings and pack -- stale ones give silently wrong
     features.  Network computes both once per frame from the frame's own table (`_knn_center`) and checks the table's
-    identity and version before every use (`_stage_features`).
+    identity and version before every use (`_render_rays`).
     count (int32[1] on the device, optional, with rows): the list's real length; M is then a capacity.
     pack: point_pack(...) of the same per-point inputs (built here when the renderer's kernel applies and the caller
     did not cache it)."""

@@ -250,10 +250,7 @@ def canonical_mlp_hip(cm, xyz, knn_idxs, net, knn_base, point_sdf, ctx, bf16):
         table = ops.point_table(knn_base.detach().double().contiguous(), point_sdf.detach().reshape(-1).float().contiguous(),
                                 pc.detach().contiguous(), ctx['bound32'], ctx['two_bound32'], enc.embeddings.detach(),
                                 enc.offsets, enc.log2_per_level_scale, enc.base_resolution)
-        _, raw_d, enc_in = ops.sample_features(
-            xyz.detach().contiguous(), knn_idxs, net.point_base.detach(), ctx['normals'], ctx['unit'],
-            net.point_counter.detach(), table, ctx['bound32'], ctx['two_bound32'], enc.embeddings.detach(), enc.offsets,
-            enc.log2_per_level_scale, enc.base_resolution, want_enc_in=True)
+        _, raw_d, enc_in = net._sample_features(xyz.detach().contiguous(), knn_idxs, table, want_enc_in=True)
         dist = raw_d[:, 4:5]
         knn40 = knn_idxs.reshape(N, -1)
         atts, var = train_ops.agg_weights(net.point_counter.detach().float().contiguous(), knn40)
@@ -266,7 +263,7 @@ def canonical_mlp_hip(cm, xyz, knn_idxs, net, knn_base, point_sdf, ctx, bf16):
         feats = torch.cat((feats, pc), dim=-1)                                       # [P,35]
         agg = ops.aggregate(feats, knn40, atts)
         raw4 = train_ops.canonical_trunks(cm, agg, var, h, bf16, fused=bool(net.cfg.get('train_fused_trunks', True)),
-                                          packed_f32=net._packed_weights()['cnl'] if bf16 else None)
+                                          packed_f32=net._packed_weights().cnl if bf16 else None)
     return torch.cat((raw4, dist), dim=-1)
 
 
@@ -291,23 +288,22 @@ def render_rays_autograd(net, rays8, Rs, Ts, vol, bbox_min, bbox_scale, bgcolor,
     center = None
     with torch.no_grad():
         if not cfg.ignore_non_rigid_motions:
-            pk = net._packed_weights()
-            condv = cond.reshape(-1).float().contiguous()
+            pk = net._packed_weights().exact()        # (the fp32 kernel, whatever cfg.mlp_precision the renderer runs at)
+            flag = None
             if bf16 and cfg.get('train_nonrigid_f16x3', True):
                 # bf16 step: the offsets (no gradient reaches this MLP, occnerf_mlp.py:144-167) on the fp32-grade split-fp16
                 # kernels (csrc/split.h; <= 1e-6 m from the fp32 kernel, 2.6x faster)
                 # (its out-of-domain flag is copied behind the step and looked at when a later step starts: a step whose
                 # activations reached the f16x3 clamp raises there -- Network.check_f16x3_domain)
                 flag = net._f16x3_flag_word() if cfg.get('f16x3_domain_check', True) else None
-                xyz = ops.nonrigid_bf16x3(cnl, condv, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], net._nonrigid_f16_pack(),
-                                          domain_flag=flag)
-                if flag is not None:
-                    net._f16x3_enqueue_check(flag, 'training step')
-            else:
-                xyz = ops.nonrigid(cnl, condv, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'])
+                pk = net._packed_weights().train_f16x3(flag)
+            xyz = pk.offsets(cnl, cond.reshape(-1).float().contiguous(), hann)
+            if flag is not None:
+                net._f16x3_enqueue_check(flag, 'training step')
         if cfg.get('knn_center_cache', True) and cfg.get('knn_culling', True):
-            # the renderer's exact centre cache: queries inside the proven radius around the collapse point take its lists
-            center = net._knn_center_lists(cond.reshape(-1).float().contiguous(), hann)
+            # the renderer's exact centre cache: queries inside the proven radius around the collapse point take its
+            # lists (no table: the feature row of the renderer's record is not wanted here)
+            center = net._knn_center(cond.reshape(-1).float().contiguous(), hann)
         knn = ops.msknn_clustered(xyz, n, S, ctx['clusters'], ctx['seed'], center=center)
     with torch.autocast('cuda', enabled=False):
         knn_base, sdf = point_sdf_block(net) if point_block is None else point_block

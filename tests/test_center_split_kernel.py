@@ -97,7 +97,7 @@ def scene(ops):
                                           net._host3(data['cnl_bbox_min_xyz']), net._host3(data['cnl_bbox_scale_xyz']))
     lrows, lcount = ops.live_rows(mask_f)
     pk = net._packed_weights()
-    ops.nonrigid_rows(xyz_f, lrows, lcount, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'])
+    ops.nonrigid_rows(xyz_f, lrows, lcount, cond, hann, pk.nr_w0, pk.nr_b0, pk.nr)
     live = (mask_f.view(-1, S) != 0)
     ray = int(live.sum(1).argmax())
     body = xyz_f.view(-1, S, 3)[ray][live[ray]].cpu().numpy()

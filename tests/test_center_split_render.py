@@ -1,4 +1,4 @@
-"""GPU: whole frames with cfg.center_split on against off (csrc/center.hip, Network._stage_features): the classification
+"""GPU: whole frames with cfg.center_split on against off (csrc/center.hip, Network._render_rays): the classification
 stage takes the collapsed samples out of the kNN and feature kernels' list and the canonical MLP reads the centre row for
 them -- rgb, alpha, depth and the per-sample raw values must not move by a bit, on every path that goes through the stage."""
 import numpy as np
@@ -114,3 +114,40 @@ def test_radius_zero_takes_nothing():
     assert float(center[0][3]) == 0.0, 'pose 10 is the recorded radius-0 frame'
     n_live, n_taken, _ = _same_frames(net, data)
     assert n_live > 0 and n_taken == 0
+
+
+def test_stale_centre_is_refused_before_any_feature_launch():
+    """The centre record carries what its cached feature row was computed from (table, visibility counter, embeddings).  A
+    record from before a counter update must not reach the feature kernel -- its row would be silently wrong
+    (ops.sample_features' freshness contract) -- and a record of the frame's own versions renders."""
+    from occnerf_amd import ops, seeded, synth
+    from occnerf_amd.modules import hann_window_weights
+    net = seeded.build_network(seed=0, S=32, non_rigid=True, device=DEV)
+    data = seeded.frame_to_device(synth.make_frame(img_size=16, pose72=synth.seeded_pose(1), orbit_frame=28), DEV)
+    nr = net.cfg.non_rigid_motion_mlp
+    wc = net._weight_constants()
+    stale = net._knn_center(data['dst_posevec'].float().reshape(-1).contiguous(),
+                            hann_window_weights(nr.multires, 1e7, nr.kick_in_iter, nr.full_band_iter).tolist(), wc['table'],
+                            net._point_pack(wc))
+    assert stale.row is not None and stale.stamp == net._center_stamp(wc['table'])
+    torch.autograd.graph.increment_version(net.point_counter)          # (what a training step's counter update does)
+    launches, real = [], ops.sample_features
+
+    def sample_features(*a, **k):
+        launches.append(a[0].shape[0])
+        return real(*a, **k)
+    ops.sample_features = sample_features
+    try:
+        net._knn_center = lambda *a, **k: stale                        # the frame is handed the old record ...
+        with torch.no_grad(), pytest.raises(RuntimeError, match='stale kNN centre'):
+            net(**data, iter_val=1e7)
+        assert launches == [], 'refused before the feature kernel ran'
+        del net._knn_center                                            # ... and then builds its own
+        with torch.no_grad():
+            out = net(**data, iter_val=1e7)
+    finally:
+        ops.sample_features = real
+        net.__dict__.pop('_knn_center', None)
+    torch.cuda.synchronize()
+    assert len(launches) == 2 and launches[0] == 8, 'the centre\'s own row, then the frame\'s samples'
+    assert bool(torch.isfinite(out['rgb']).all()) and float(out['alpha'].max()) > 0.0, 'the frame is not empty'

@@ -169,7 +169,7 @@ def test_pose_mesh_with_the_non_rigid_offset(ops, seeded_non_rigid):
     n = x_skel.shape[0]
     back = ops.nonrigid_rows(x_skel.clone(), torch.arange(n, device=DEV, dtype=torch.int32),
                              torch.full((1,), n, device=DEV, dtype=torch.int32), data['dst_posevec'].reshape(-1),
-                             hann, pk['nr_w0'], pk['nr_b0'], pk['nr'])
+                             hann, pk.nr_w0, pk.nr_b0, pk.nr)
     ok = flag.cpu().numpy() == 0
     args = (Rs.cpu().numpy(), Ts.cpu().numpy(), vol.cpu().numpy()[:24], bmin, bsc)
     _, _, J = mp.warp(p.cpu().numpy().astype(np.float64), *args)

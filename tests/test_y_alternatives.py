@@ -214,16 +214,16 @@ def test_f16x3_reports_leaving_its_domain():
     # (a)
     net, _ = build_network(int(g['meta.seed']), util.level(g), S=int(g['meta.S']), non_rigid=nr, mlp_precision='f16x3')
     pk = net._packed_weights()
-    assert pk['domain_flag'] is not None and int(pk['domain_flag'].item()) == 0
+    assert pk.domain_flag is not None and int(pk.domain_flag.item()) == 0
     x = torch.randn(1000, 68, device=DEV) * 0.3
     raw = torch.zeros(1000, 5, device=DEV)
-    ops.canonical_mlp_bf16x3(x, pk['cnl'], pk['cnl_bf16'], raw, domain_flag=pk['domain_flag'])
-    assert int(pk['domain_flag'].item()) == 0
+    ops.canonical_mlp_bf16x3(x, pk.cnl, pk.cnl_split, raw, domain_flag=pk.domain_flag)
+    assert int(pk.domain_flag.item()) == 0
     big = x.clone()
     big[777, :34] = 5000.0                                  # 16 x 5000 > 65504: the input clamp itself
-    ops.canonical_mlp_bf16x3(big, pk['cnl'], pk['cnl_bf16'], raw, domain_flag=pk['domain_flag'])
-    assert int(pk['domain_flag'].item()) == 1
-    pk['domain_flag'].zero_()
+    ops.canonical_mlp_bf16x3(big, pk.cnl, pk.cnl_split, raw, domain_flag=pk.domain_flag)
+    assert int(pk.domain_flag.item()) == 1
+    pk.domain_flag.zero_()
     # (b)
     with warnings.catch_warnings():
         warnings.simplefilter('error')

@@ -44,7 +44,7 @@ if __name__ == '__main__':
     for _ in range(6):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        ops.nonrigid(xyz, cond, hann, pk['nr_w0'], pk['nr_b0'], pk['nr'], out=xyz)
+        ops.nonrigid(xyz, cond, hann, pk.nr_w0, pk.nr_b0, pk.nr, out=xyz)
         b.record()
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b))
