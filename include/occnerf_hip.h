@@ -820,6 +820,32 @@ int occnerf_mesh_emit(const float *field, int32_t nx, int32_t ny, int32_t nz, fl
 int occnerf_mesh_vertices(const int64_t *keys, int64_t V, const float *field, int32_t nx, int32_t ny, int32_t nz,
                           float level, const double *h_bbox_min, double h, float *pos, void *stream);
 
+/* Connected components of a welded triangle mesh (occnerf_amd/mesh.py component_table).  The reference
+ * has no counterpart of these two entries.  Two triangles are connected when they share a vertex index; a component is a set
+ * of vertices and its label is the smallest vertex index in it; a vertex no face names is a component of its own.  Integer
+ * atomics only: every output is a pure function of the inputs, bit-identical to tests/mesh_components_restatement.py.
+ * T, V < 2^31. */
+
+/* No counterpart in the reference.  One pass over labels[V] int32, IN/OUT, which the caller starts at labels[v] = v: per
+ * triangle of faces[T,3] int32 the smallest of its three labels is written by an atomic minimum into the three vertices and
+ * into the vertices their labels name, then every labels[v] is replaced by the top of its chain.  Every store lowers a word
+ * and labels[v] <= v holds throughout.  status[2] int32: [0] is set to 1 when the pass lowered a word (the caller zeroes it
+ * before the pass and repeats passes until it stays 0: the labels are then final), [1] is set to 1 when a face names a vertex
+ * outside [0, V) or labels[] holds a value no pass can have written (such a face or vertex is left alone).  No workgroup
+ * waits on another.  V = 0 returns 0 without a launch. */
+int occnerf_mesh_label_pass(const int32_t *faces, int64_t T, int64_t V, int32_t *labels, int32_t *status, void *stream);
+/* No counterpart in the reference.  The records of the C components, indexed by rank (the components in ascending label
+ * order): vrank[V] int32 is the rank of every vertex's component.  With s = llrint(((float64(verts) - h_bbox_min) / h) * 1024)
+ * per axis, one rounding per operator, held to [-2^30, 2^30] (NaN: the lower end): counts[C,3] int32 += the component's
+ * vertices, triangles (a triangle belongs to the component of its first vertex) and boundary vertices (some s[a] is 0 or
+ * (n[a] - 1) * 1024); box[C,6] int32 = min / max with smin[3], smax[3]; vol6[C] int64 += det(s_a, s_b, s_c) over the triangles
+ * in two's-complement arithmetic with wrap-around.  The caller zeroes counts and vol6 and fills box with INT32_MAX x 3,
+ * INT32_MIN x 3.  h_bbox_min[3]: HOST, double.  Every axis has 2 .. 2^20 points.  A face that names a vertex outside [0, V)
+ * and a rank outside [0, C) add nothing.  V = 0 or C = 0 returns 0 without a launch. */
+int occnerf_mesh_component_stats(const float *verts, int64_t V, const int32_t *faces, int64_t T, const int32_t *vrank,
+                                 int64_t C, const double *h_bbox_min, double h, int32_t nx, int32_t ny, int32_t nz,
+                                 int32_t *counts, int32_t *box, int64_t *vol6, void *stream);
+
 /* No counterpart in the reference.  The exported mesh in a frame's pose: x_c[V,3] float32 canonical
  * positions -> p_out[V,3] float32 with F(p) = x_c, F the skeletal warp of occnerf_sample_warp in fp64 on the float32 Rs[nb,3,3],
  * Ts[nb,3], vol[nb,G,G,G] (the background channel dropped) and the HOST h_bbox_min[3] / h_bbox_scale[3].  Per vertex: the bones

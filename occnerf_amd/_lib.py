@@ -146,6 +146,8 @@ SIGNATURES = {
     'occnerf_mesh_count': (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _vp]),
     'occnerf_mesh_emit': (C.c_int, [_vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp, _vp]),
     'occnerf_mesh_vertices': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _f32, _vp, C.c_double, _vp, _vp]),
+    'occnerf_mesh_label_pass': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
+    'occnerf_mesh_component_stats': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_pose': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_project': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_raster': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),

@@ -133,8 +133,10 @@ _DEFAULTS = {
     'warp_bone_culling': True,       # warp kernel skips bones whose weight channel cannot reach a wave's samples (same bits)
     # run.py --type mesh (occnerf_amd/mesh.py): resolution = voxels along the longest axis of the canonical box; level = the
     # iso density, None: ln 2 / h (one voxel edge of matter half opaque); normals: write vertex normals; chunk: points per
-    # Network.query_canonical chunk
-    'mesh': {'resolution': 256, 'level': None, 'normals': True, 'chunk': 1 << 21},
+    # Network.query_canonical chunk; components: 'all' (nothing is labelled), 'largest' (only the connected component with the
+    # most triangles stays) or a number f in (0, 1] (every component with at least f x the largest one's triangles stays);
+    # drop_cavities: also drop closed components that enclose negative volume
+    'mesh': {'resolution': 256, 'level': None, 'normals': True, 'chunk': 1 << 21, 'components': 'all', 'drop_cavities': False},
     # run.py --type mesh, the mesh in the pose of frames (occnerf_amd/mesh.py export_posed): frames = None
     # (canonical mesh only), a list of frame indices of the movement source, or 'all'; candidates / max_iter / tol = the bones
     # tried per vertex, the Newton steps per bone and the residual (metres, on the fp64 iterate) that counts as converged;

@@ -7,6 +7,10 @@ counterpart there.
                  welding (torch.cumsum, torch.unique) as plumbing between the launches;
   export_mesh    grid, surface, vertex colours by a second query at the vertices, host float64 area-weighted normals, a binary
                  little-endian PLY and a JSON sidecar;
+  component_table, select_components, filter_mesh
+                 the opt-in clean-up between the surface and the colours (mesh.components,
+                 mesh.drop_cavities): connected components labelled in HIP (csrc/mesh_components.hip), an integer record per
+                 component, detached blobs dropped by their triangle count and closed shells of negative volume as cavities;
   pose_mesh      the vertices in the pose of a frame: the frame's non-rigid offset undone by a fixed point
                  on the renderer's own kernel (Network.unoffset_canonical), then the skeletal warp inverted per vertex by a
                  damped Newton iteration in HIP (csrc/mesh_pose.hip) -- the model only knows the map from a frame to the
@@ -15,7 +19,7 @@ counterpart there.
                  and posed.json.
 
 Every step is a pure function of its inputs: the same checkpoint and settings give the same PLY byte for byte (the sidecars
-differ in their wall times only).  Floater removal, decimation, smoothing, OBJ and a mesh welded from the f16x3 kernels' field
+differ in their wall times only).  Decimation, smoothing, hole filling, OBJ and a mesh welded from the f16x3 kernels' field
 are not offered; nor, for the posed mesh, roots of the warp other than the owning bone's or changes of topology."""
 import json
 import math
@@ -92,6 +96,99 @@ def extract_mesh(field, level, bbox_min, h):
     return ops.mesh_vertices(keys, field, level, bbox_min, h), inverse.reshape(T, 3).to(torch.int32)
 
 
+# ------------------------------------------------------------------ connected components
+SNAP = 1024                  # the records' coordinates: 1/1024 of a voxel edge from the box minimum
+TABLE_ROWS = 16
+
+
+def check_components(components):
+    """mesh.components as select_components takes it: 'all', 'largest' or a float in (0, 1]; anything else is refused by name."""
+    if isinstance(components, str):
+        if components in ('all', 'largest'):
+            return components
+    elif isinstance(components, (int, float, np.integer, np.floating)) and not isinstance(components, (bool, np.bool_)):
+        if 0.0 < float(components) <= 1.0:
+            return float(components)
+    raise RuntimeError(f"mesh.components = {components!r}: 'all', 'largest' or a number in (0, 1] (the share of the largest "
+                       "component's triangle count a component needs to stay)")
+
+
+def check_drop_cavities(drop_cavities):
+    if not isinstance(drop_cavities, (bool, np.bool_)):
+        raise RuntimeError(f'mesh.drop_cavities = {drop_cavities!r}: True or False')
+    return bool(drop_cavities)
+
+
+def component_table(verts, faces, bbox_min, h, shape):
+    """(labels int32 [V] on the device, records, passes): ops.mesh_components on the mesh verts float32 [V,3] / faces int32
+    [T,3] over the grid `shape` = (nx, ny, nz) of voxel edge h at bbox_min, the records brought to the host with one copy per
+    column: a dict of numpy arrays, one row per component in ascending label order (label, vertices, triangles,
+    boundary_vertices int32 [C]; smin, smax int32 [C,3]; volume6_q int64 [C])."""
+    labels, rec = ops.mesh_components(verts, faces, bbox_min, h, shape)
+    return labels, {k: rec[k].cpu().numpy() for k in ops.MESH_RECORD_COLUMNS}, int(rec['passes'])
+
+
+def component_verdicts(records, components='all', drop_cavities=False):
+    """Per component 'kept', 'small' (the size rule dropped it) or 'cavity' (the size rule kept it; it has no boundary vertex
+    and a negative volume).  The size rule comes first and is relative to the largest component of the whole mesh: 'largest'
+    keeps the component with the most triangles (ties: the smaller label), a number f every one with triangles >= f * that
+    count (in float64)."""
+    components, drop_cavities = check_components(components), check_drop_cavities(drop_cavities)
+    tri = np.asarray(records['triangles'], dtype=np.int64).reshape(-1)
+    n = tri.shape[0]
+    if n == 0:
+        return []
+    if components == 'all':
+        keep = np.ones(n, dtype=bool)
+    elif components == 'largest':
+        keep = np.zeros(n, dtype=bool)
+        keep[int(np.argmax(tri))] = True               # the first of equals: the rows ascend by label
+    else:
+        keep = tri.astype(np.float64) >= np.float64(components) * np.float64(tri.max())
+    cavity = (np.asarray(records['boundary_vertices']).reshape(-1) == 0) & \
+        (np.asarray(records['volume6_q'], dtype=np.int64).reshape(-1) < 0)
+    return ['small' if not k else ('cavity' if drop_cavities and c else 'kept') for k, c in zip(keep, cavity)]
+
+
+def select_components(records, components='all', drop_cavities=False):
+    """bool [C]: which components stay.  A pure host function of the record table."""
+    return np.array([v == 'kept' for v in component_verdicts(records, components, drop_cavities)], dtype=bool)
+
+
+def filter_mesh(verts, faces, labels, keep):
+    """(verts [V',3], faces int32 [T',3]) on the device of verts: the components whose flag in keep (bool [C], ascending label
+    order) is set.  Kept vertices and triangles keep their order; the indices are remapped by the exclusive scan of the
+    vertices' keep flags.  Plumbing: torch indexing and one cumsum."""
+    dev = verts.device
+    keep = torch.as_tensor(np.asarray(keep, dtype=bool), device=dev)
+    vrank, roots = ops.mesh_component_ranks(labels)
+    if keep.shape != roots.shape:
+        raise RuntimeError(f'filter_mesh: keep holds {tuple(keep.shape)} flags for {int(roots.numel())} components')
+    keep_v = keep[vrank.long()] if vrank.numel() else torch.zeros(0, dtype=torch.bool, device=dev)
+    new_index = (torch.cumsum(keep_v, 0, dtype=torch.int32) - keep_v.to(torch.int32))
+    keep_t = keep_v[faces[:, 0].long()]
+    return verts[keep_v].contiguous(), new_index[faces[keep_t].long()].reshape(-1, 3).contiguous()
+
+
+def components_report(records, verdicts, components, drop_cavities, passes, h, bbox_min):
+    """The sidecar's 'components' entry."""
+    tri, nv = records['triangles'].astype(np.int64), records['vertices'].astype(np.int64)
+    kept = np.array([v == 'kept' for v in verdicts], dtype=bool)
+    lo = np.asarray(bbox_min, dtype=np.float64).reshape(3)
+    unit = float(h) / SNAP
+    rows = []
+    for r in sorted(range(len(verdicts)), key=lambda r: (-int(tri[r]), r))[:TABLE_ROWS]:
+        rows.append({'label': int(records['label'][r]), 'vertices': int(nv[r]), 'triangles': int(tri[r]),
+                     'volume_m3': float(records['volume6_q'][r]) * unit ** 3 / 6.0,
+                     'boundary_vertices': int(records['boundary_vertices'][r]),
+                     'box_min': (lo + records['smin'][r].astype(np.float64) * unit).tolist(),
+                     'box_max': (lo + records['smax'][r].astype(np.float64) * unit).tolist(),
+                     'verdict': verdicts[r]})
+    return {'policy': {'components': components, 'drop_cavities': bool(drop_cavities)}, 'found': len(verdicts),
+            'kept': int(kept.sum()), 'dropped_vertices': int(nv[~kept].sum()), 'dropped_triangles': int(tri[~kept].sum()),
+            'cavities_dropped': sum(v == 'cavity' for v in verdicts), 'passes': int(passes), 'largest': rows}
+
+
 def boundary_inside(field, level):
     """Inside grid points on the six boundary faces: where there are any the surface meets the grid's boundary and is open."""
     inside = field > float(np.float32(level))
@@ -123,9 +220,15 @@ def write_ply(path, verts, faces, colors, normals=None):
         out.write(f.tobytes())
 
 
-def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, normals=True, chunk=1 << 21, keep=None):
+def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, normals=True, chunk=1 << 21, keep=None,
+                components='all', drop_cavities=False):
     """<out_dir>/mesh.ply and mesh.json of the canonical body -> the sidecar's dict.  keep: a dict that receives what
-    export_posed needs of the mesh ('verts' float32 [V,3] on the device, 'faces' int32 [T,3] and 'colors' uint8 [V,3] numpy)."""
+    export_posed needs of the mesh ('verts' float32 [V,3] on the device, 'faces' int32 [T,3] and 'colors' uint8 [V,3] numpy).
+    components / drop_cavities: the clean-up of DESIGN.md section 7m; at their defaults nothing is labelled and the files are
+    those written without them.  Otherwise the colours, the normals and `keep` are those of the kept mesh, and the sidecar
+    gains 'components', 'extracted_vertices' / 'extracted_triangles' and seconds['components']."""
+    components, drop_cavities = check_components(components), check_drop_cavities(drop_cavities)
+    cleaning = components != 'all' or drop_cavities
     dev = net.point_base.device
 
     def clock():
@@ -138,7 +241,14 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
     lo = np.asarray(bbox_min, dtype=np.float32).reshape(3).astype(np.float64)
     verts, faces = extract_mesh(field, used, lo, h)
     on_boundary = boundary_inside(field, used)
-    t2 = clock()
+    t2 = t_clean = clock()
+    if cleaning:
+        extracted = (int(verts.shape[0]), int(faces.shape[0]))
+        labels, records, passes = component_table(verts, faces, lo, h, (nx, ny, nz))
+        verdicts = component_verdicts(records, components, drop_cavities)
+        verts, faces = filter_mesh(verts, faces, labels, [v == 'kept' for v in verdicts])
+        report = components_report(records, verdicts, components, drop_cavities, passes, h, lo)
+        t_clean = clock()
     rgb = torch.sigmoid(net.query_canonical(verts, chunk=chunk)[:, :3])
     colors = to_8b_image(rgb.cpu().numpy())
     t3 = clock()
@@ -154,7 +264,10 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
     info = {'resolution': int(resolution), 'h': h, 'level': float(np.float32(used)), 'level_is_default': level is None,
             'grid_shape_xyz': [nx, ny, nz], 'vertices': int(v.shape[0]), 'triangles': int(f.shape[0]),
             'inside_points_on_boundary': on_boundary, 'normals': bool(normals),
-            'seconds': {'grid': round(t1 - t0, 4), 'extract': round(t2 - t1, 4), 'colour': round(t3 - t2, 4)}}
+            'seconds': {'grid': round(t1 - t0, 4), 'extract': round(t2 - t1, 4), 'colour': round(t3 - t_clean, 4)}}
+    if cleaning:
+        info.update(extracted_vertices=extracted[0], extracted_triangles=extracted[1], components=report)
+        info['seconds']['components'] = round(t_clean - t2, 4)
     with open(os.path.join(out_dir, 'mesh.json'), 'w') as out:
         json.dump(info, out, indent=1)
         out.write('\n')

@@ -1415,6 +1415,109 @@ def mesh_vertices(keys, field, level, bbox_min, h):
     return pos
 
 
+# ------------------------------------------------------------------ connected components of the mesh
+MESH_LABEL_MAX_PASSES = 256
+MESH_RECORD_COLUMNS = ('label', 'vertices', 'triangles', 'boundary_vertices', 'smin', 'smax', 'volume6_q')
+
+
+def _mesh_faces(who, faces, V, dev):
+    pf = _chk(faces, torch.int32, f'{who}: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != dev:
+        raise RuntimeError(f'{who}: faces must be int32 [T,3] on the device of the vertices, got {tuple(faces.shape)}')
+    T = int(faces.shape[0])
+    if T >= 1 << 31 or V >= 1 << 31:
+        raise RuntimeError(f'{who}: T = {T} / V = {V} reach the limit of 2^31')
+    return pf, T
+
+
+def mesh_label(faces, V, max_passes=MESH_LABEL_MAX_PASSES):
+    """(labels int32 [V] on the device of faces, passes): labels[v] = the smallest vertex index of v's component of the mesh
+    faces int32 [T,3] over V vertices (occnerf_mesh_label_pass, repeated until a pass changes nothing; one blocking read of
+    two words per pass).  A face that names a vertex outside [0, V) and max_passes passes without a fixed point raise; partial
+    labels are never returned."""
+    if not torch.is_tensor(faces):
+        raise RuntimeError('mesh_label: faces must be a tensor')
+    V, max_passes = int(V), int(max_passes)
+    if V < 0 or max_passes < 1:
+        raise RuntimeError(f'mesh_label: V = {V} must be >= 0 and max_passes = {max_passes} >= 1')
+    pf, T = _mesh_faces('mesh_label', faces, V, faces.device)
+    labels = torch.arange(V, device=faces.device, dtype=torch.int32)
+    if V == 0:
+        if T:
+            raise RuntimeError(f'mesh_label: {T} faces over no vertex')
+        return labels, 0
+    status = torch.zeros(2, device=faces.device, dtype=torch.int32)
+    for passes in range(1, max_passes + 1):
+        status.zero_()
+        with _guard(faces):
+            rc = _lib.lib().occnerf_mesh_label_pass(pf if T else None, T, V, labels.data_ptr(), status.data_ptr(), _stream(faces))
+        _lib.check(rc, 'mesh_label_pass')
+        changed, bad = status.tolist()
+        if bad:
+            raise RuntimeError(f'mesh_label: a face names a vertex outside [0, {V})')
+        if not changed:
+            return labels, passes
+    raise RuntimeError(f'mesh_label: no pass left the labels unchanged within max_passes = {max_passes} ({T} triangles, {V} vertices)')
+
+
+def mesh_component_ranks(labels):
+    """(vrank int32 [V], roots int32 [C]): the rank of every vertex's component among the components in ascending label order,
+    and the labels in that order.  Plumbing (torch.cumsum) between the launches; C is read back with one blocking copy."""
+    V = int(labels.numel())
+    is_root = labels == torch.arange(V, device=labels.device, dtype=torch.int32)
+    rank = (torch.cumsum(is_root, 0, dtype=torch.int32) - 1)
+    return rank[labels.long()].contiguous(), torch.nonzero(is_root).reshape(-1).to(torch.int32)
+
+
+def mesh_component_stats(verts, faces, vrank, n_comp, bbox_min, h, shape):
+    """The records of the n_comp = C components (occnerf_mesh_component_stats; include/occnerf_hip.h): verts float32 [V,3], faces int32
+    [T,3], vrank int32 [V] (mesh_component_ranks), bbox_min[3] / h on the host, shape = (nx, ny, nz) of the grid -> (counts
+    int32 [C,3]: vertices, triangles, boundary vertices; box int32 [C,6]: smin, smax; vol6 int64 [C]) on the device."""
+    pv = _chk(verts, torch.float32, 'mesh_component_stats: verts')
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError(f'mesh_component_stats: verts must be float32 [V,3], got {tuple(verts.shape)}')
+    V, dev, n_comp = int(verts.shape[0]), verts.device, int(n_comp)
+    pf, T = _mesh_faces('mesh_component_stats', faces, V, dev)
+    pr = _chk(vrank, torch.int32, 'mesh_component_stats: vrank')
+    if tuple(vrank.shape) != (V,) or vrank.device != dev:
+        raise RuntimeError(f'mesh_component_stats: vrank must be int32 [{V}] on the device of verts')
+    nx, ny, nz = (int(s) for s in shape)
+    h = float(h)
+    if not (0.0 < h < float('inf')) or min(nx, ny, nz) < 2 or max(nx, ny, nz) > 1 << 20 or not 0 <= n_comp <= V:
+        raise RuntimeError(f'mesh_component_stats: h = {h} must be positive and finite, every axis of the {nx} x {ny} x {nz} grid '
+                           f'2 .. 2^20 points, C = {n_comp} within [0, V = {V}]')
+    counts = torch.zeros(n_comp, 3, device=dev, dtype=torch.int32)
+    box = torch.empty(n_comp, 6, device=dev, dtype=torch.int32)
+    box[:, :3], box[:, 3:] = torch.iinfo(torch.int32).max, torch.iinfo(torch.int32).min
+    vol6 = torch.zeros(n_comp, device=dev, dtype=torch.int64)
+    if V == 0 or n_comp == 0:
+        return counts, box, vol6
+    bmin = np.ascontiguousarray(np.asarray(bbox_min, dtype=np.float64).reshape(3))
+    with _guard(verts):
+        rc = _lib.lib().occnerf_mesh_component_stats(pv, V, pf if T else None, T, pr, n_comp, bmin.ctypes.data_as(C.c_void_p), h, nx, ny,
+                                                     nz, counts.data_ptr(), box.data_ptr(), vol6.data_ptr(), _stream(verts))
+    _lib.check(rc, 'mesh_component_stats')
+    return counts, box, vol6
+
+
+def mesh_components(verts, faces, bbox_min, h, shape, max_passes=MESH_LABEL_MAX_PASSES):
+    """(labels int32 [V], records) of the mesh verts float32 [V,3] / faces int32 [T,3]: labels[v] = the
+    smallest vertex index connected to v through faces; records: a dict of device tensors, one row per component in ascending
+    label order -- label, vertices, triangles, boundary_vertices int32 [C], smin, smax int32 [C,3] (the box in 1/1024 voxel
+    from bbox_min), volume6_q int64 [C] -- and 'passes', the labelling passes taken (an int)."""
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError('mesh_components: verts must be a float32 [V,3] tensor')
+    _chk(verts, torch.float32, 'mesh_components: verts')
+    if not torch.is_tensor(faces) or faces.device != verts.device:
+        raise RuntimeError('mesh_components: faces must be a tensor on the device of verts')
+    labels, passes = mesh_label(faces, int(verts.shape[0]), max_passes)
+    vrank, roots = mesh_component_ranks(labels)
+    counts, box, vol6 = mesh_component_stats(verts, faces, vrank, int(roots.numel()), bbox_min, h, shape)
+    return labels, {'label': roots, 'vertices': counts[:, 0].contiguous(), 'triangles': counts[:, 1].contiguous(),
+                    'boundary_vertices': counts[:, 2].contiguous(), 'smin': box[:, :3].contiguous(),
+                    'smax': box[:, 3:].contiguous(), 'volume6_q': vol6, 'passes': passes}
+
+
 def mesh_pose(x_c, Rs, Ts, vol, bbox_min, bbox_scale, candidates=3, max_iter=20, tol=1e-7):
     """Observation-space positions of canonical points (occnerf_mesh_pose): x_c float32 [V,3], Rs [nb,3,3],
     Ts [nb,3] and vol [>= nb,G,G,G] (only the first nb channels are read: the background channel is dropped) as

@@ -304,9 +304,14 @@ def run_mesh():
                              'source has none (set train.dataset_path or movement.dataset)')
         kept = {} if posing or viewing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
-                           normals=bool(m.normals), chunk=int(m.chunk), keep=kept)
+                           normals=bool(m.normals), chunk=int(m.chunk), keep=kept, components=m.get('components', 'all'),
+                           drop_cavities=m.get('drop_cavities', False))
         print(f"mesh: {info['vertices']} vertices, {info['triangles']} triangles on a {info['grid_shape_xyz']} grid at level "
               f"{info['level']:g} -> {os.path.join(out_dir, 'mesh.ply')}")
+        if 'components' in info:
+            c = info['components']
+            print(f"mesh: {c['kept']} of {c['found']} components kept ({c['passes']} labelling passes): {c['dropped_vertices']} "
+                  f"vertices and {c['dropped_triangles']} triangles dropped, {c['cavities_dropped']} of the components as cavities")
         if posing:
             # the mesh in the pose of frames of the movement source: its body constants only
             cfg.ignore_non_rigid_motions = ignore_non_rigid
