@@ -860,6 +860,30 @@ int occnerf_mesh_pose(const float *x_c, int64_t V, const float *Rs, const float 
                       const float *h_bbox_min, const float *h_bbox_scale, int32_t candidates, int32_t max_iter, double tol,
                       float *p_out, uint8_t *flag, uint8_t *iters, float *resid, void *stream);
 
+/* The exported mesh as a rig.  The reference has no counterpart of these two entries.  fp64 on the
+ * float32 inputs, one rounding per operator in the order of tests/mesh_rig_restatement.py, no atomics: the same bytes on every run. */
+
+/* No counterpart in the reference.  x_c[V,3] float32 canonical positions -> the K (4 or 8) influences per vertex from the
+ * motion-weight volume vol[nb,G,G,G] (the background channel dropped; HOST h_bbox_min[3] / h_bbox_scale[3]): c_b = the
+ * trilinear tap of bone b's channel at x_c (that of occnerf_mesh_pose); the bones with c_b > 0 by descending c_b (ties: the
+ * lower index), the first n <= K of them; s = their sum in that order, total = sum_b c_b in index order.  joints[V,K] uint8
+ * and weights[V,K] float32 = float32(c_k / s) in that order, unused slots joint 0 and weight 0; count[V] uint8 = n; kept[V]
+ * float32 = float32(s / total).  n = 0: joint 0 with weight 1, kept 0.  nb <= 32, 2 <= G <= 1024.  V = 0 returns 0 without a
+ * launch. */
+int occnerf_mesh_skin(const float *x_c, int64_t V, const float *vol, int32_t nb, int32_t G, const float *h_bbox_min,
+                      const float *h_bbox_scale, int32_t K, uint8_t *joints, float *weights, uint8_t *count, float *kept,
+                      void *stream);
+/* No counterpart in the reference.  Forward linear blend skinning of x_c[V,3] with joints[V,K] / weights[V,K] (K 4 or 8) for F
+ * frames at once: Rs[F,nb,3,3], Ts[F,nb,3] are the backward bases (observation -> canonical) of the frames;
+ * posed[F,V,3] = float32(sum_k w_k R_b^T (x - T_b)) over the slots with w_k != 0, in slot order.  A slot whose joint index is
+ * >= nb adds nothing (callers refuse such an index before the call).  With target[F,V,3] float32 and target_flag[F,V] uint8
+ * (both or neither; NULL: posed only): M = sum_k w_k R_b^T, M d = target - p (the unrounded p) by Cramer's rule;
+ * delta[F,V,3] = float32(d), dflag[F,V] = 0; d = 0 and dflag = 1 where det M is 0 or not finite, target_flag != 0, or not every
+ * |d_c| <= max_delta (finite, >= 0).  1 <= F <= 65535, nb <= 32, V < 2^31.  V = 0 returns 0 without a launch. */
+int occnerf_mesh_lbs(const float *x_c, int64_t V, const uint8_t *joints, const float *weights, int32_t K, const float *Rs,
+                     const float *Ts, int32_t F, int32_t nb, const float *target, const uint8_t *target_flag, double max_delta,
+                     float *posed, float *delta, uint8_t *dflag, void *stream);
+
 /* A triangle mesh seen through a pinhole camera (occnerf_amd/mesh_view.py, run.py --type mesh mesh_view.frames; DESIGN.md
  * section 7j).  The reference has no counterpart of these three entries: it draws no geometry.  Bit-identical to
  * tests/mesh_raster_restatement.py; the same bytes on every run.  Limits: 1 <= H, W <= 16384 and H * W <= 2^28; T, V < 2^31. */

@@ -149,6 +149,8 @@ SIGNATURES = {
     'occnerf_mesh_label_pass': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp]),
     'occnerf_mesh_component_stats': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, C.c_double, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_pose': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    'occnerf_mesh_skin': (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'occnerf_mesh_lbs': (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, C.c_double, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_project': (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_raster': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     'occnerf_mesh_resolve': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),

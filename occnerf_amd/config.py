@@ -142,6 +142,14 @@ _DEFAULTS = {
     # tried per vertex, the Newton steps per bone and the residual (metres, on the fp64 iterate) that counts as converged;
     # non_rigid: undo the frame's non-rigid offset too; world: write R(Rh) p + Th instead of the body's own space
     'mesh_pose': {'frames': None, 'candidates': 3, 'max_iter': 20, 'tol': 1e-7, 'non_rigid': True, 'world': False},
+    # run.py --type mesh, the mesh as a rigged, animated glTF (occnerf_amd/mesh.py export_rig): enable
+    # writes mesh/rigged.glb and rig.json; frames = None (the rigged rest pose), a list of frame indices of the movement source,
+    # or 'all': the keys of the animation, fps of them per second; influences: 4 or 8 joints per vertex; correctives: store per
+    # frame the difference between the rig's linear blend skinning and the model's own posed mesh (the mesh_pose keys apply) as
+    # a morph target -- at most max_correctives frames, each target is vertices x 12 bytes --, none longer than max_delta metres;
+    # world: a node above the root carries R(Rh), Th
+    'mesh_rig': {'enable': False, 'frames': None, 'influences': 4, 'fps': 30.0, 'correctives': False, 'max_correctives': 16,
+                 'max_delta': 0.05, 'world': False},
     # run.py --type mesh, the posed mesh seen from its frame's camera (occnerf_amd/mesh_view.py export_views, DESIGN.md section
     # 7j): frames = None (nothing happens), a list of frame indices of the movement source's prepared dataset, or 'all'; per
     # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the

@@ -16,7 +16,11 @@ counterpart there.
                  damped Newton iteration in HIP (csrc/mesh_pose.hip) -- the model only knows the map from a frame to the
                  canonical body;
   export_posed   posed/<frame name>.ply per frame -- the faces and colours of mesh.ply, the posed vertices, their normals --
-                 and posed.json.
+                 and posed.json;
+  skin_mesh, rig_frames, export_rig
+                 the mesh as a rig (mesh_rig.enable): skin weights read off the motion-weight volume and
+                 forward linear blend skinning in HIP (csrc/mesh_rig.hip), the frames' joint transforms as keys of one
+                 animation, rigged.glb (occnerf_amd/gltf.py) and rig.json.
 
 Every step is a pure function of its inputs: the same checkpoint and settings give the same PLY byte for byte (the sidecars
 differ in their wall times only).  Decimation, smoothing, hole filling, OBJ and a mesh welded from the f16x3 kernels' field
@@ -348,23 +352,33 @@ class PoseFrames:
 _POSE_KEYS = ('dst_Rs', 'dst_Ts', 'dst_posevec', 'cnl_gtfms', 'motion_weights_priors')
 
 
+def _frame_indices(source, frames, key):
+    idxs = list(range(len(source))) if isinstance(frames, str) and frames == 'all' else [int(i) for i in (frames or [])]
+    for i in idxs:
+        if not 0 <= i < len(source):
+            raise RuntimeError(f'{key}: frame {i} outside the {len(source)} frames of the source')
+    return idxs
+
+
+def _device_frame(fr, dev):
+    data = {k: torch.from_numpy(np.ascontiguousarray(fr[k])).to(dev) for k in _POSE_KEYS}
+    data.update({k: np.asarray(fr[k], dtype=np.float32) for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz')})
+    return data
+
+
 def export_posed(net, out_dir, kept, source, frames, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, world=False,
                  normals=True, iter_val=1e7):
     """<out_dir>/posed/<frame name>.ply for the frames (indices into `source`, a PoseFrames; 'all': every one) and
     <out_dir>/posed.json -> its dict.  kept: what export_mesh(keep=...) left of mesh.ply: every posed PLY has its faces and
     colours, the posed vertices and (normals) the normals recomputed from them."""
     dev = net.point_base.device
-    idxs = list(range(len(source))) if isinstance(frames, str) and frames == 'all' else [int(i) for i in frames]
-    for i in idxs:
-        if not 0 <= i < len(source):
-            raise RuntimeError(f'mesh_pose.frames: frame {i} outside the {len(source)} frames of the source')
+    idxs = _frame_indices(source, frames, 'mesh_pose.frames')
     verts, faces, colors = kept['verts'], kept['faces'], kept['colors']
     os.makedirs(os.path.join(out_dir, 'posed'), exist_ok=True)
     V, per_frame = int(verts.shape[0]), []
     for i in idxs:
         name, fr, Rh, Th = source.frame(i)
-        data = {k: torch.from_numpy(np.ascontiguousarray(fr[k])).to(dev) for k in _POSE_KEYS}
-        data.update({k: np.asarray(fr[k], dtype=np.float32) for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz')})
+        data = _device_frame(fr, dev)
         stats = {}
         p, flag, iters, resid = pose_mesh(net, verts, data, candidates, max_iter, tol, non_rigid, iter_val, stats)
         t0 = time.perf_counter()
@@ -382,6 +396,191 @@ def export_posed(net, out_dir, kept, source, frames, candidates=3, max_iter=20, 
     info = {'vertices': V, 'candidates': int(candidates), 'max_iter': int(max_iter), 'tol': float(tol),
             'non_rigid': bool(non_rigid and not net.cfg.ignore_non_rigid_motions), 'world': bool(world), 'frames': per_frame}
     with open(os.path.join(out_dir, 'posed.json'), 'w') as out:
+        json.dump(info, out, indent=1)
+        out.write('\n')
+    return info
+
+
+# ------------------------------------------------------------------ the mesh as a rig
+RIG_DEFAULTS = {'enable': False, 'frames': None, 'influences': 4, 'fps': 30.0, 'correctives': False, 'max_correctives': 16,
+                'max_delta': 0.05, 'world': False}
+
+
+def check_rig(rig):
+    """The mesh_rig keys as export_rig takes them (a dict with every key of RIG_DEFAULTS); a value out of range is refused by
+    name."""
+    rig = {k: (rig.get(k, v) if hasattr(rig, 'get') else v) for k, v in RIG_DEFAULTS.items()}
+
+    def number(v):
+        return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    for k in ('enable', 'correctives', 'world'):
+        if not isinstance(rig[k], (bool, np.bool_)):
+            raise RuntimeError(f'mesh_rig.{k} = {rig[k]!r}: True or False')
+    if not number(rig['influences']) or rig['influences'] not in (4, 8):
+        raise RuntimeError(f"mesh_rig.influences = {rig['influences']!r}: 4 or 8 (JOINTS_0 / WEIGHTS_0, or those and JOINTS_1 / WEIGHTS_1)")
+    if not number(rig['fps']) or not 0.0 < float(rig['fps']) < float('inf'):
+        raise RuntimeError(f"mesh_rig.fps = {rig['fps']!r}: a positive finite number of keys per second")
+    if not number(rig['max_delta']) or not 0.0 <= float(rig['max_delta']) < float('inf'):
+        raise RuntimeError(f"mesh_rig.max_delta = {rig['max_delta']!r}: a finite number of metres >= 0")
+    if not isinstance(rig['max_correctives'], (int, np.integer)) or isinstance(rig['max_correctives'], (bool, np.bool_)) \
+            or rig['max_correctives'] < 1:
+        raise RuntimeError(f"mesh_rig.max_correctives = {rig['max_correctives']!r}: a whole number >= 1")
+    frames = rig['frames']
+    if not (frames is None or frames == 'all' or (isinstance(frames, (list, tuple)) and all(
+            isinstance(i, (int, np.integer)) and not isinstance(i, (bool, np.bool_)) for i in frames))):
+        raise RuntimeError(f"mesh_rig.frames = {frames!r}: None, 'all' or a list of frame indices")
+    return rig
+
+
+def skin_mesh(net, verts, data, influences=4, iter_val=1e7):
+    """(joints uint8 [V,K], weights float32 [V,K], count uint8 [V], kept float32 [V]) on the device: the K = influences (4 or
+    8) skinning influences of the canonical vertices, read off the model's motion-weight volume as Network.render_preamble
+    returns it (the background channel dropped) by ops.mesh_skin.  The volume is decoded from the subject's priors and the
+    module's constants, not from the pose: the `data` of any one frame of the subject serves, and every frame gives the same
+    bytes."""
+    Rs, _, vol = net.render_preamble(data, iter_val)
+    return ops.mesh_skin(verts.detach().contiguous(), vol[:Rs.shape[0]], ops.host_float3(data['cnl_bbox_min_xyz']),
+                         ops.host_float3(data['cnl_bbox_scale_xyz']), K=influences)
+
+
+def joint_transforms(Rs, Ts, cnl_gtfms):
+    """G [nb,4,4] float64 = inv([R_b | T_b]) cnl_gtfms_b: where the frame puts every joint, from the frame's backward bases
+    (observation -> canonical, float32 [nb,3,3] / [nb,3]) and the canonical global transforms [nb,4,4]."""
+    R, T = np.asarray(Rs, dtype=np.float32).astype(np.float64), np.asarray(Ts, dtype=np.float32).astype(np.float64)
+    A = np.tile(np.eye(4), (R.shape[0], 1, 1))
+    A[:, :3, :3], A[:, :3, 3] = R, T
+    return np.linalg.inv(A) @ np.asarray(cnl_gtfms, dtype=np.float32).astype(np.float64)
+
+
+def local_keys(G, previous=None):
+    """(rotation [nb,4] float64 unit quaternions (x, y, z, w), translation [nb,3] float64) of the local transforms
+    L_b = inv(G_parent) G_b over synth.SMPL_PARENT, L_0 = G_0; previous: the last key's quaternions, for the sign."""
+    from .gltf import PARENTS, quaternion
+    rot, tra = np.zeros((G.shape[0], 4)), np.zeros((G.shape[0], 3))
+    for b in range(G.shape[0]):
+        L = G[b] if PARENTS[b] < 0 else np.linalg.inv(G[PARENTS[b]]) @ G[b]
+        rot[b], tra[b] = quaternion(L[:3, :3], None if previous is None else previous[b]), L[:3, 3]
+    return rot, tra
+
+
+def rig_frames(net, source, frames, iter_val=1e7):
+    """The skeleton's keys for the frames (indices into `source`, a PoseFrames; 'all': every one) -> a dict: 'index', 'name',
+    'data' (the frames' device constants) per frame; 'Rs' [F,nb,3,3] / 'Ts' [F,nb,3] on the device, the backward bases of
+    Network.render_preamble with the pose refiner in them; 'G' [F,nb,4,4] float64, the global joint transforms
+    inv([R_b | T_b]) cnl_gtfms_b; 'rotation' [F,nb,4] / 'translation' [F,nb,3] float64, the local transforms over
+    synth.SMPL_PARENT as unit quaternions (Shepperd's branch; the sign of the non-negative dot product with the key before) and
+    offsets -- the offset is written per key: it is the rest offset up to the float32 rounding inside Rs / Ts, and with it the
+    file reproduces G; 'world_rotation' [F,4] / 'world_translation' [F,3]: R(Rh) and Th, what to_world applies."""
+    from .gltf import quaternion
+    dev = net.point_base.device
+    out = {k: [] for k in ('index', 'name', 'data', 'Rs', 'Ts', 'G', 'rotation', 'translation', 'world_rotation', 'world_translation')}
+    for i in _frame_indices(source, frames, 'mesh_rig.frames'):
+        name, fr, Rh, Th = source.frame(i)
+        data = _device_frame(fr, dev)
+        Rs, Ts, _ = net.render_preamble(data, iter_val)
+        G = joint_transforms(Rs.cpu().numpy(), Ts.cpu().numpy(), fr['cnl_gtfms'])
+        rot, tra = local_keys(G, out['rotation'][-1] if out['rotation'] else None)
+        wq = quaternion(np.asarray(Rh, dtype=np.float32).astype(np.float64), out['world_rotation'][-1] if out['world_rotation'] else None)
+        for k, v in (('index', i), ('name', name), ('data', data), ('Rs', Rs), ('Ts', Ts), ('G', G), ('rotation', rot),
+                     ('translation', tra), ('world_rotation', wq), ('world_translation', np.asarray(Th, dtype=np.float32).astype(np.float64))):
+            out[k].append(v)
+    if out['index']:
+        out['Rs'], out['Ts'] = torch.stack(out['Rs']).contiguous(), torch.stack(out['Ts']).contiguous()
+        for k in ('G', 'rotation', 'translation', 'world_rotation', 'world_translation'):
+            out[k] = np.stack(out[k])
+    return out
+
+
+def _spread(d):
+    d = np.asarray(d, dtype=np.float64)
+    if d.size == 0:
+        return {'vertices': 0, 'mean': None, 'p99': None, 'max': None}
+    return {'vertices': int(d.size), 'mean': float(d.mean()), 'p99': float(np.percentile(d, 99)), 'max': float(d.max())}
+
+
+def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, normals=True, iter_val=1e7):
+    """<out_dir>/rigged.glb and rig.json -> the sidecar's dict: the kept mesh of export_mesh(keep=...) with a skeleton, skin
+    weights (skin_mesh) and, for rig['frames'] of `source` (a PoseFrames), the capture's motion as one animation (rig_frames).
+    rig: the mesh_rig keys (RIG_DEFAULTS).  No frames: the rigged rest pose.  Per animated frame rig.json holds how far the
+    rig's linear blend skinning (ops.mesh_lbs) is from the model's own posed mesh (pose_mesh with candidates / max_iter / tol /
+    non_rigid, over its converged vertices); rig['correctives'] stores that difference as one morph target per frame, so that
+    at its key time the file shows the model's mesh.  rig['world']: a node above the root carries R(Rh), Th."""
+    from . import gltf
+    rig = check_rig(RIG_DEFAULTS if rig is None else rig)
+    dev = net.point_base.device
+    K, correct = int(rig['influences']), bool(rig['correctives'])
+
+    def clock():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    verts, faces, colors = kept['verts'], kept['faces'], kept['colors']
+    V = int(verts.shape[0])
+    if V == 0 or len(faces) == 0:
+        raise RuntimeError(f'mesh_rig: the mesh has {V} vertices and {len(faces)} triangles: there is nothing to rig (on a '
+                           'checkpoint without a surface at the default level set mesh.level)')
+    idxs = _frame_indices(source, rig['frames'], 'mesh_rig.frames')
+    if correct and len(idxs) > int(rig['max_correctives']):
+        raise RuntimeError(f"mesh_rig.correctives: {len(idxs)} frames are more than mesh_rig.max_correctives = "
+                           f"{int(rig['max_correctives'])}: every frame adds a morph target of {V} x 12 bytes to the file")
+    t0 = clock()
+    keys = rig_frames(net, source, idxs, iter_val)
+    t1 = clock()
+    fr0 = source.frame(idxs[0] if idxs else 0)[1]               # the subject's constants: any frame has them
+    cnl, data0 = np.asarray(fr0['cnl_gtfms']), keys['data'][0] if idxs else _device_frame(fr0, dev)
+    joints, weights, count, kept_share = skin_mesh(net, verts, data0, K, iter_val)
+    t2 = clock()
+    F, per_frame, delta = len(idxs), [], None
+    t_pose = t_lbs = 0.0
+    if F:
+        targets, flags = [], []
+        for f in range(F):
+            ta = clock()
+            p, flag, _, _ = pose_mesh(net, verts, keys['data'][f], candidates, max_iter, tol, non_rigid, iter_val)
+            targets.append(p), flags.append(flag)
+            t_pose += clock() - ta
+        ta = clock()
+        target, tflag = torch.stack(targets).contiguous(), torch.stack(flags).contiguous()
+        x = verts.detach().contiguous()
+        if correct:
+            posed, delta, dflag = ops.mesh_lbs(x, joints, weights, keys['Rs'], keys['Ts'], target, tflag, float(rig['max_delta']))
+        else:
+            posed = ops.mesh_lbs(x, joints, weights, keys['Rs'], keys['Ts'])
+        t_lbs = clock() - ta
+        rest = gltf.rest_translations(cnl)
+        dist = (posed.double() - target.double()).norm(dim=2).cpu().numpy()
+        solved = tflag.cpu().numpy() == 0
+        for f in range(F):
+            row = {'frame': idxs[f], 'name': keys['name'][f], 'lbs_to_model_m': _spread(dist[f][solved[f]]),
+                   'translation_minus_rest_offset_max_m': float(np.abs(keys['translation'][f] - rest).max())}
+            if correct:
+                row.update(corrective_flagged=int(dflag[f].sum().item()), corrective_stored=int(V - dflag[f].sum().item()),
+                           corrective_max_m=float(delta[f].abs().max().item()))
+            per_frame.append(row)
+    t3 = clock()
+    v = verts.cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    size = gltf.write_glb(
+        os.path.join(out_dir, 'rigged.glb'), v, faces, colors, joints.cpu().numpy(), weights.cpu().numpy(), cnl,
+        normals=vertex_normals(v, faces) if normals else None,
+        animation={'rotation': keys['rotation'], 'translation': keys['translation']} if F else None,
+        world={'rotation': keys['world_rotation'], 'translation': keys['world_translation']} if F and rig['world'] else None,
+        correctives=delta.cpu().numpy() if correct and F else None, fps=float(rig['fps']))
+    t4 = time.perf_counter()
+    n, share = count.cpu().numpy(), kept_share.cpu().numpy().astype(np.float64)
+    bound = share[n > 0]
+    info = {'K': K, 'vertices': V, 'triangles': int(len(faces)), 'bytes': int(size), 'fps': float(rig['fps']),
+            'influences_histogram': np.bincount(n, minlength=K + 1).tolist(), 'bound_to_root_for_want_of_a_bone': int((n == 0).sum()),
+            'kept_share': {'min': float(bound.min()) if bound.size else None, 'mean': float(bound.mean()) if bound.size else None,
+                           'p01': float(np.percentile(bound, 1)) if bound.size else None},
+            'joint_names': list(gltf.JOINT_NAMES), 'joint_parents': list(gltf.PARENTS),
+            'axes': "the body's own space, as mesh.ply: x body left, y up, z front of the canonical body, metres; nothing is "
+                    "rotated to glTF's +Y-up, +Z-front convention and nothing is rescaled",
+            'correctives': correct, 'max_delta': float(rig['max_delta']), 'world': bool(rig['world']),
+            'candidates': int(candidates), 'max_iter': int(max_iter), 'tol': float(tol),
+            'non_rigid': bool(non_rigid and not net.cfg.ignore_non_rigid_motions), 'frames': per_frame,
+            'seconds': {'keys': round(t1 - t0, 4), 'skin': round(t2 - t1, 4), 'pose': round(t_pose, 4), 'lbs': round(t_lbs, 4),
+                        'report': round(t3 - t2 - t_pose - t_lbs, 4), 'write': round(t4 - t3, 4)}}
+    with open(os.path.join(out_dir, 'rig.json'), 'w') as out:
         json.dump(info, out, indent=1)
         out.write('\n')
     return info

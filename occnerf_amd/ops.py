@@ -1557,6 +1557,93 @@ def mesh_pose(x_c, Rs, Ts, vol, bbox_min, bbox_scale, candidates=3, max_iter=20,
     return p, flag, iters, resid
 
 
+# ------------------------------------------------------------------ the mesh as a rig
+def mesh_skin(x_c, vol, bbox_min, bbox_scale, K=4):
+    """The K (4 or 8) skinning influences of canonical points (occnerf_mesh_skin): x_c float32 [V,3], vol [nb,G,G,G]: what
+    Network.render_preamble returns with the background channel dropped (vol[:nb], as mesh_pose reads it), bbox_min[3] / bbox_scale[3] on the host ->
+    (joints uint8 [V,K], weights float32 [V,K], count uint8 [V], kept float32 [V]) on the device of x_c.  V = 0 launches
+    nothing."""
+    px = _chk(x_c, torch.float32, 'mesh_skin: x_c')
+    if x_c.dim() != 2 or x_c.shape[1] != 3:
+        raise RuntimeError(f'mesh_skin: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    pv = _chk(vol, torch.float32, 'mesh_skin: vol')
+    K = int(K)
+    if K not in (4, 8):
+        raise RuntimeError(f'mesh_skin: K = {K} is neither 4 nor 8')
+    if vol.dim() != 4 or not (vol.shape[1] == vol.shape[2] == vol.shape[3]) or vol.device != x_c.device:
+        raise RuntimeError(f'mesh_skin: vol must be [nb,G,G,G] on the device of x_c, got {tuple(vol.shape)}')
+    nb = int(vol.shape[0])
+    if not 1 <= nb <= 32:
+        raise RuntimeError(f'mesh_skin: nb = {nb} outside 1..32 (drop the background channel: vol[:nb])')
+    V, dev = int(x_c.shape[0]), x_c.device
+    joints = torch.empty(V, K, device=dev, dtype=torch.uint8)
+    weights = torch.empty(V, K, device=dev, dtype=torch.float32)
+    count = torch.empty(V, device=dev, dtype=torch.uint8)
+    kept = torch.empty(V, device=dev, dtype=torch.float32)
+    if V == 0:
+        return joints, weights, count, kept
+    _kmin, pmin = _host_f32(bbox_min, 3)
+    _ksc, psc = _host_f32(bbox_scale, 3)
+    with _guard(x_c):
+        rc = _lib.lib().occnerf_mesh_skin(px, V, pv, nb, int(vol.shape[-1]), pmin, psc, K, joints.data_ptr(), weights.data_ptr(),
+                                          count.data_ptr(), kept.data_ptr(), _stream(x_c))
+    _lib.check(rc, 'mesh_skin')
+    return joints, weights, count, kept
+
+
+def mesh_lbs(x_c, joints, weights, Rs, Ts, target=None, target_flag=None, max_delta=0.05, joints_checked=False):
+    """Forward linear blend skinning of the rig for F frames at once (occnerf_mesh_lbs): x_c float32 [V,3], mesh_skin's joints
+    uint8 [V,K] / weights float32 [V,K], the frames' backward bases Rs [F,nb,3,3] / Ts [F,nb,3] -> posed float32 [F,V,3]; with
+    target float32 [F,V,3] and target_flag uint8 [F,V] -> (posed, delta float32 [F,V,3], dflag uint8 [F,V]): the displacement
+    of the canonical vertex that makes its skinned position the target, 0 and flagged where it is not to be had or exceeds
+    max_delta.  A joint index >= nb is refused by name before anything is launched (one blocking read of the joints' maximum;
+    joints_checked=True: the caller has made that test).  V = 0 launches nothing."""
+    px = _chk(x_c, torch.float32, 'mesh_lbs: x_c')
+    if x_c.dim() != 2 or x_c.shape[1] != 3:
+        raise RuntimeError(f'mesh_lbs: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    V, dev = int(x_c.shape[0]), x_c.device
+    pj, pw = _chk(joints, torch.uint8, 'mesh_lbs: joints'), _chk(weights, torch.float32, 'mesh_lbs: weights')
+    K = int(joints.shape[1]) if joints.dim() == 2 else -1
+    if K not in (4, 8) or tuple(joints.shape) != (V, K) or tuple(weights.shape) != (V, K):
+        raise RuntimeError(f'mesh_lbs: joints and weights must be [{V},K] with K 4 or 8, got {tuple(joints.shape)} and '
+                           f'{tuple(weights.shape)}')
+    pR, pT = _chk(Rs, torch.float32, 'mesh_lbs: Rs'), _chk(Ts, torch.float32, 'mesh_lbs: Ts')
+    F, nb = (int(Rs.shape[0]), int(Rs.shape[1])) if Rs.dim() == 4 else (-1, -1)
+    if F < 1 or nb < 1 or tuple(Rs.shape) != (F, nb, 3, 3) or tuple(Ts.shape) != (F, nb, 3):
+        raise RuntimeError(f'mesh_lbs: Rs must be [F,nb,3,3] and Ts [F,nb,3] with F >= 1, got {tuple(Rs.shape)} and {tuple(Ts.shape)}')
+    if not 1 <= nb <= 32 or F > 65535:
+        raise RuntimeError(f'mesh_lbs: nb = {nb} outside 1..32 or F = {F} above 65535')
+    max_delta = float(max_delta)
+    if not (0.0 <= max_delta < float('inf')):
+        raise RuntimeError(f'mesh_lbs: max_delta = {max_delta} must be a finite number >= 0')
+    if (target is None) != (target_flag is None):
+        raise RuntimeError('mesh_lbs: target and target_flag come together')
+    pt = pf = None
+    if target is not None:
+        pt, pf = _chk(target, torch.float32, 'mesh_lbs: target'), _chk(target_flag, torch.uint8, 'mesh_lbs: target_flag')
+        if tuple(target.shape) != (F, V, 3) or tuple(target_flag.shape) != (F, V):
+            raise RuntimeError(f'mesh_lbs: target must be [{F},{V},3] and target_flag [{F},{V}], got {tuple(target.shape)} and '
+                               f'{tuple(target_flag.shape)}')
+    if not all(t.device == dev for t in (joints, weights, Rs, Ts) + (() if target is None else (target, target_flag))):
+        raise RuntimeError('mesh_lbs: every tensor must be on the device of x_c')
+    if V and not joints_checked:
+        hi = int(joints.max().item())
+        if hi >= nb:
+            raise RuntimeError(f'mesh_lbs: joint index {hi} outside [0, {nb})')
+    posed = torch.empty(F, V, 3, device=dev, dtype=torch.float32)
+    delta = dflag = None
+    if target is not None:
+        delta = torch.empty(F, V, 3, device=dev, dtype=torch.float32)
+        dflag = torch.empty(F, V, device=dev, dtype=torch.uint8)
+    if V:
+        with _guard(x_c):
+            rc = _lib.lib().occnerf_mesh_lbs(px, V, pj, pw, K, pR, pT, F, nb, pt, pf, max_delta, posed.data_ptr(),
+                                             None if delta is None else delta.data_ptr(),
+                                             None if dflag is None else dflag.data_ptr(), _stream(x_c))
+        _lib.check(rc, 'mesh_lbs')
+    return posed if target is None else (posed, delta, dflag)
+
+
 # ------------------------------------------------------------------ the mesh seen through a camera (DESIGN.md section 7j)
 MESH_RASTER_COUNTS = ('index', 'near', 'guard', 'area', 'offscreen', 'wide', 'covered')
 MESH_RASTER_MAX_SIDE, MESH_RASTER_MAX_PIXELS = 16384, 1 << 28

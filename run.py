@@ -6,7 +6,8 @@ Frames go to experiments/<category>/<task>/<subject>/<experiment>/<load_net>/<fo
 exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seeded[:N]` renders the
 seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on disk.  `--type mesh` writes no frames but
 <...>/<load_net>/mesh/mesh.ply and mesh.json; with `mesh_pose.frames` also mesh/posed/<frame name>.ply and mesh/posed.json;
-with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json (run_mesh below).
+with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json; with `mesh_rig.enable True`
+also mesh/rigged.glb, the mesh with a skeleton, skin weights and the motion of `mesh_rig.frames`, and mesh/rig.json (run_mesh below).
 `show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
 `geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
 `--type animate animate.motion PATH` drives the subject of a prepared dataset with a motion it has not seen (occnerf_amd/
@@ -281,7 +282,11 @@ def run_mesh():
     the pose of those frames of the movement source -> mesh/posed/<frame name>.ply and mesh/posed.json.  With mesh_view.frames
     set, also the posed mesh seen from the camera of those frames of the movement source's prepared dataset (occnerf_amd/
     mesh_view.py) -> mesh/view/<frame name>.png, the mesh beside the photograph, and mesh/view.json with
-    the silhouette's IoU against the frame's mask.  Rank 0 alone works."""
+    the silhouette's IoU against the frame's mask.  With mesh_rig.enable, also the kept mesh as a rigged glTF binary (occnerf_amd/
+    mesh.py export_rig) -> mesh/rigged.glb: 24 SMPL joints, skin weights from the motion-weight volume, the
+    frames mesh_rig.frames of the movement source as one animation (none: the rest pose), with mesh_rig.correctives a morph
+    target per frame that closes the gap to the model's own posed mesh; mesh/rig.json says how large that gap is.  Rank 0 alone
+    works."""
     from occnerf_amd.mesh import PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
     cfg.ignore_non_rigid_motions = True
@@ -302,7 +307,12 @@ def run_mesh():
         if viewing and resolve_dataset_path(cfg, 'movement') is None:
             raise SystemExit('mesh_view.frames: the silhouette is held against the masks of a prepared dataset; the synthetic frame '
                              'source has none (set train.dataset_path or movement.dataset)')
-        kept = {} if posing or viewing else None
+        mrig = cfg.get('mesh_rig') or {}
+        rigging = bool(mrig.get('enable', False))
+        if rigging:
+            from occnerf_amd.mesh import check_rig
+            mrig = check_rig(mrig)
+        kept = {} if posing or viewing or rigging else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
                            normals=bool(m.normals), chunk=int(m.chunk), keep=kept, components=m.get('components', 'all'),
                            drop_cavities=m.get('drop_cavities', False))
@@ -323,6 +333,23 @@ def run_mesh():
             for f in posed['frames']:
                 print(f"posed {f['name']}: {f['not_converged']} not converged, {f['no_bone']} without a bone of {posed['vertices']} "
                       f"vertices, worst residual {f['worst_resid']:.3g} m, {f['mean_iters']:.2f} Newton steps per vertex")
+        if rigging:
+            # the kept mesh with a skeleton, skin weights and the frames' motion as one glTF
+            from occnerf_amd.mesh import export_rig
+            cfg.ignore_non_rigid_motions = ignore_non_rigid
+            source = PoseFrames(resolve_dataset_path(cfg, 'movement'), total_frames=int(cfg.render_frames),
+                                bbox_offset=float(cfg.bbox_offset), volume_size=int(cfg.mweight_volume.volume_size))
+            rigged = export_rig(model, out_dir, kept, source, mrig, candidates=int(mp.get('candidates', 3)),
+                                max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
+                                non_rigid=bool(mp.get('non_rigid', True)), normals=bool(m.normals), iter_val=cfg.eval_iter)
+            print(f"rig: {rigged['vertices']} vertices with up to {rigged['K']} joints each ({rigged['bound_to_root_for_want_of_a_bone']} "
+                  f"bound to the root for want of a bone), {len(rigged['frames'])} keys -> {os.path.join(out_dir, 'rigged.glb')} "
+                  f"({rigged['bytes']} bytes)")
+            for f in rigged['frames']:
+                d = f['lbs_to_model_m']
+                if d['vertices']:
+                    print(f"rig {f['name']}: linear blend skinning is {d['mean']:.3g} m (mean), {d['p99']:.3g} m (99 %), {d['max']:.3g} m "
+                          f"(max) from the model's mesh over {d['vertices']} solved vertices")
         if viewing:
             # the posed mesh through each frame's own camera, against the frame's mask: the dataset as
             # --type movement opens it, so K, the mask and the photograph are those of the training size
