@@ -912,6 +912,38 @@ int occnerf_mesh_resolve(const uint64_t *keys, const int32_t *faces, int64_t T, 
                          const uint8_t *vflag, const uint8_t *colors, const uint8_t *h_bgcolor, int32_t H, int32_t W,
                          uint8_t *cover, int32_t *tri, float *depth, uint8_t *rgb, int32_t *counts, void *stream);
 
+/* The texture of the exported mesh (occnerf_amd/mesh.py bake_texture, run.py --type mesh mesh_texture.enable; DESIGN.md section
+ * 7o).  The reference has no counterpart of these three entries.  A per-triangle atlas: with n the cell edge in texels
+ * (4 <= n <= 64) and m = n - 3, triangles 2c and 2c + 1 share the n x n cell c at column c % C, row c / C of the atlas; the even
+ * one owns the texels (column i, row j) of the cell with i + j <= n - 2, the odd one those with i' + j' <= n - 2, i' = n - 1 - i,
+ * j' = n - 1 - j; P = n (n - 1) / 2 texels each, numbered by ascending j', then ascending i' (the even triangle: i' = i, j' = j).
+ * Bit-identical to tests/mesh_texture_restatement.py; no atomics, the same bytes on every run. */
+
+/* No counterpart in the reference.  verts[V,3] float32, faces[T,3] int32 -> pts[T,P,3] float32: texel (i', j') of a triangle
+ * (v0, v1, v2) is float32(((f64(m - i' - j') v0 + f64(i') v1) + f64(j') v2) / f64(m)) per coordinate, one rounding per fp64
+ * operator; the texels (0,0), (m,0), (0,m) reproduce the vertices.  A face with an index outside [0, V): its P rows are NaN
+ * and status[0] (int32, zeroed by the caller) becomes 1; no such index is used as an address.  T P < 2^31.  T = 0 returns 0
+ * without a launch. */
+int occnerf_mesh_texel_points(const float *verts, int64_t V, const int32_t *faces, int64_t T, int32_t n, float *pts,
+                              int32_t *status, void *stream);
+/* No counterpart in the reference.  rgb[T P,3] float32 (the colours of occnerf_mesh_texel_points' rows) -> the owned texels of
+ * atlas[H,W,3] uint8, IN/OUT: uint8(255.0f * min(max(c, 0), 1)) with the product in float32 and truncation, 0 for a NaN; every
+ * other byte of the atlas is left as the caller filled it.  W = C n and ceil(ceil(T / 2) / C) n <= H <= 16384 are required.
+ * T = 0 returns 0 without a launch. */
+int occnerf_mesh_texture_fill(const float *rgb, int64_t T, int32_t n, int32_t C, int32_t H, int32_t W, uint8_t *atlas,
+                              void *stream);
+/* No counterpart in the reference.  The textured twin of occnerf_mesh_resolve: keys[Himg*Wimg] of occnerf_mesh_raster ->
+ * rgb[Himg*Wimg,3] uint8.  A hit pixel: the winner t and its perspective-correct weights as occnerf_mesh_resolve forms them
+ * (a vertex with z = 0 is a flagged one), put back into the face's own vertex order; x = min(max(w1 m, 0), m),
+ * y = min(max(w2 m, 0), m - x); the taps (floor x + {0,1}, floor y + {0,1}) clamped to [0, n - 1] of t's own frame, weights
+ * (1-ax)(1-ay), ax(1-ay), (1-ax)ay, ax ay, each read from atlas[aH,aW,3] through t's cell and, for an odd t, the mirror;
+ * s = ((w00 c00 + w10 c10) + w01 c01) + w11 c11 in fp64, rounded to nearest even, clamped to 0..255.  Every other pixel: the
+ * HOST h_bgcolor[3] uint8.  The atlas must hold T triangles as occnerf_mesh_texture_fill requires.  T = 0 or V = 0: the
+ * background everywhere. */
+int occnerf_mesh_resolve_textured(const uint64_t *keys, const int32_t *faces, int64_t T, int64_t V, const int32_t *xy,
+                                  const double *z, int32_t Himg, int32_t Wimg, const uint8_t *atlas, int32_t aH, int32_t aW,
+                                  int32_t n, int32_t C, const uint8_t *h_bgcolor, uint8_t *rgb, void *stream);
+
 /* Collapsed samples, classified once in front of the kNN and feature kernels (no counterpart in the
  * reference).  One lane per entry o of the live list rows[0 .. *n_dev) (capacity N_max): flag[o] = 1 iff xyz[rows[o]] lies
  * inside the radius of center[4] (the |p - c|^2 < r^2 test of the kNN and feature kernels) AND the encoder input x[4] the

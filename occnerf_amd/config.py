@@ -150,6 +150,11 @@ _DEFAULTS = {
     # world: a node above the root carries R(Rh), Th
     'mesh_rig': {'enable': False, 'frames': None, 'influences': 4, 'fps': 30.0, 'correctives': False, 'max_correctives': 16,
                  'max_delta': 0.05, 'world': False},
+    # run.py --type mesh, the mesh's colour as a texture (occnerf_amd/mesh.py export_texture): enable
+    # writes mesh/texture.png and texture.json and puts the image into rigged.glb (mesh_rig.enable) or else into a static
+    # mesh/textured.glb, in place of the vertex colours; cell: the edge in texels (4..64) of the atlas cell two triangles share
+    # -- a triangle's edge spans cell - 3 texels --; fill: the colour 0..255 of the texels no triangle owns
+    'mesh_texture': {'enable': False, 'cell': 8, 'fill': [0, 0, 0]},
     # run.py --type mesh, the posed mesh seen from its frame's camera (occnerf_amd/mesh_view.py export_views, DESIGN.md section
     # 7j): frames = None (nothing happens), a list of frame indices of the movement source's prepared dataset, or 'all'; per
     # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the

@@ -1,10 +1,12 @@
-"""A glTF 2.0 binary (.glb) writer for the rigged body: struct, json and numpy only.
+"""A glTF 2.0 binary (.glb) writer for the rigged body (DESIGN.md sections 7n and 7o): struct, json and numpy only.
 
 One mesh primitive (POSITION, optionally NORMAL, COLOR_0 as normalised bytes, JOINTS_n / WEIGHTS_n, uint32 indices), one skin of
 the 24 SMPL joints, optionally one animation (a rotation and a translation channel per joint, LINEAR; a node above the root for
 the world placement; one morph target per key with a STEP weights channel).  The file is in the body's own space: nothing is
 rotated to glTF's +Y-up convention and nothing is rescaled.  The same inputs give the same bytes: no date, no host name, JSON
-with sorted keys.  Textures, materials beyond vertex colours, cameras and several scenes are not written."""
+with sorted keys.  With texture= the primitive is unwelded (three vertices per triangle, TEXCOORD_0 into the per-triangle atlas of
+DESIGN.md section 7o, no COLOR_0) and carries one PNG image, one sampler, one texture and one material; with joints=None the mesh
+is static.  Normal maps, several materials, cameras and several scenes are not written."""
 import json
 import struct
 
@@ -20,6 +22,7 @@ N_JOINTS = len(JOINT_NAMES)
 PARENTS = [-1] + [SMPL_PARENT[b] for b in range(1, N_JOINTS)]
 FLOAT, UBYTE, UINT = 5126, 5121, 5125
 ARRAY_BUFFER, ELEMENT_ARRAY_BUFFER = 34962, 34963
+LINEAR, CLAMP_TO_EDGE = 9729, 33071
 
 
 def quaternion(R, previous=None):
@@ -79,7 +82,7 @@ class _Buffer:
 
 
 def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=None, animation=None, world=None, correctives=None,
-              fps=30.0):
+              fps=30.0, texture=None):
     """The rigged mesh as <path> (glTF 2.0 binary) -> the number of bytes written.
 
     verts float32 [V,3], faces int32 [T,3], colors uint8 [V,3], normals float32 [V,3] or None; joints uint8 [V,K] and weights
@@ -87,19 +90,36 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
     their inverses are the inverse bind matrices).  animation: None (the rest pose only) or {'rotation': [F,24,4] float64 unit
     quaternions (x, y, z, w), 'translation': [F,24,3]}: every joint's local transform per key (mesh.rig_frames), key i at
     i / fps seconds.  world: None or {'rotation': [F,4], 'translation': [F,3]}: a node above the root joint.  correctives:
-    None or float32 [F,V,3]: one morph target per key, switched on at its key by a STEP weights channel."""
+    None or float32 [F,V,3]: one morph target per key, switched on at its key by a STEP weights channel.
+
+    joints None (then weights and cnl_gtfms are not read): a static mesh -- no skin, no joint nodes, no animation.
+    texture: None or {'uv': float32 [T,3,2] (mesh.texture_uv), 'png': the atlas as the bytes of a PNG file}: every per-vertex
+    array is gathered by faces.reshape(-1), the indices are 0 .. 3T-1, TEXCOORD_0 replaces COLOR_0 (viewers multiply the two;
+    colors may be None) and the image travels inside the binary chunk.  Without texture and with joints the bytes are those
+    written before either was offered."""
     verts = np.asarray(verts, dtype='<f4').reshape(-1, 3)
     faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
     V = verts.shape[0]
-    colors = np.asarray(colors, dtype=np.uint8).reshape(V, 3)
-    joints, weights = np.asarray(joints, dtype=np.uint8), np.asarray(weights, dtype='<f4')
-    K = joints.shape[1] if joints.ndim == 2 else -1
-    if K not in (4, 8) or joints.shape != (V, K) or weights.shape != (V, K):
-        raise RuntimeError(f'write_glb: joints and weights must be [{V},K] with K 4 or 8, got {joints.shape} and {weights.shape}')
+    rigged = joints is not None
+    if texture is None or colors is not None:
+        colors = np.asarray(colors, dtype=np.uint8).reshape(V, 3)
+    K = 0
+    if rigged:
+        joints, weights = np.asarray(joints, dtype=np.uint8), np.asarray(weights, dtype='<f4')
+        K = joints.shape[1] if joints.ndim == 2 else -1
+        if K not in (4, 8) or joints.shape != (V, K) or weights.shape != (V, K):
+            raise RuntimeError(f'write_glb: joints and weights must be [{V},K] with K 4 or 8, got {joints.shape} and {weights.shape}')
+    elif animation is not None or world is not None or correctives is not None:
+        raise RuntimeError('write_glb: a mesh without joints is static: it takes no animation, world placement or correctives')
     if V == 0 or faces.shape[0] == 0:
         raise RuntimeError('write_glb: a mesh without vertices or faces cannot be written (glTF accessors hold at least one element)')
-    if joints.max() >= N_JOINTS or faces.min() < 0 or faces.max() >= V:
+    if (rigged and joints.max() >= N_JOINTS) or faces.min() < 0 or faces.max() >= V:
         raise RuntimeError(f'write_glb: a joint index reaches {N_JOINTS} or a face index lies outside [0, {V})')
+    if texture is not None:
+        uv, png = np.asarray(texture['uv'], dtype='<f4'), bytes(texture['png'])
+        if uv.shape != (faces.shape[0], 3, 2) or png[:8] != b'\x89PNG\r\n\x1a\n':
+            raise RuntimeError(f"write_glb: texture['uv'] must be float32 [{faces.shape[0]},3,2] and texture['png'] a PNG file, got "
+                               f'{uv.shape} and {len(png)} bytes')
     fps = float(fps)
     if not (0.0 < fps < float('inf')):
         raise RuntimeError(f'write_glb: fps = {fps} must be a positive finite number')
@@ -110,21 +130,54 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
         raise RuntimeError('write_glb: the world placement is animated: it needs an animation')
 
     buf = _Buffer()
+    if normals is not None:
+        normals = np.asarray(normals, dtype='<f4').reshape(V, 3)
+    indices = faces.reshape(-1).astype('<u4')
+    if texture is not None:                              # unwelded: a vertex per corner, in the order of the faces
+        corner = faces.reshape(-1)
+        verts, normals = verts[corner], None if normals is None else normals[corner]
+        if rigged:
+            joints, weights = joints[corner], weights[corner]
+        if correctives is not None:
+            correctives = np.asarray(correctives, dtype='<f4')[:, corner]
+        indices = np.arange(corner.shape[0], dtype='<u4')
     attributes = {'POSITION': buf.add(verts, FLOAT, 'VEC3', ARRAY_BUFFER, minmax=True)}
     if normals is not None:
-        attributes['NORMAL'] = buf.add(np.asarray(normals, dtype='<f4').reshape(V, 3), FLOAT, 'VEC3', ARRAY_BUFFER)
-    rgba = np.concatenate([colors, np.full((V, 1), 255, np.uint8)], 1)
-    attributes['COLOR_0'] = buf.add(rgba, UBYTE, 'VEC4', ARRAY_BUFFER, normalized=True)
+        attributes['NORMAL'] = buf.add(normals, FLOAT, 'VEC3', ARRAY_BUFFER)
+    if texture is None:
+        rgba = np.concatenate([colors, np.full((V, 1), 255, np.uint8)], 1)
+        attributes['COLOR_0'] = buf.add(rgba, UBYTE, 'VEC4', ARRAY_BUFFER, normalized=True)
+    else:
+        attributes['TEXCOORD_0'] = buf.add(uv.reshape(-1, 2), FLOAT, 'VEC2', ARRAY_BUFFER)
     for s in range(K // 4):
         attributes[f'JOINTS_{s}'] = buf.add(joints[:, 4 * s:4 * s + 4], UBYTE, 'VEC4', ARRAY_BUFFER)
         attributes[f'WEIGHTS_{s}'] = buf.add(weights[:, 4 * s:4 * s + 4], FLOAT, 'VEC4', ARRAY_BUFFER)
-    primitive = {'attributes': attributes, 'indices': buf.add(faces.reshape(-1).astype('<u4'), UINT, 'SCALAR', ELEMENT_ARRAY_BUFFER),
-                 'mode': 4}
+    primitive = {'attributes': attributes, 'indices': buf.add(indices, UINT, 'SCALAR', ELEMENT_ARRAY_BUFFER), 'mode': 4}
     mesh = {'primitives': [primitive], 'name': 'body'}
+    image_view = None
+    if texture is not None:                              # the PNG file as a buffer view of its own: no accessor, no target
+        buf.blob.extend(b'\0' * (-len(buf.blob) % 4))
+        buf.views.append({'buffer': 0, 'byteOffset': len(buf.blob), 'byteLength': len(png)})
+        buf.blob.extend(png)
+        image_view = len(buf.views) - 1
+        primitive['material'] = 0
     if correctives is not None:
         d = np.asarray(correctives, dtype='<f4')
         primitive['targets'] = [{'POSITION': buf.add(d[f], FLOAT, 'VEC3', ARRAY_BUFFER, minmax=True)} for f in range(F)]
         mesh['weights'] = [0.0] * F
+
+    if image_view is not None:
+        extras = {'images': [{'bufferView': image_view, 'mimeType': 'image/png'}],
+                  'samplers': [{'magFilter': LINEAR, 'minFilter': LINEAR, 'wrapS': CLAMP_TO_EDGE, 'wrapT': CLAMP_TO_EDGE}],
+                  'textures': [{'sampler': 0, 'source': 0}],
+                  'materials': [{'name': 'baked', 'pbrMetallicRoughness': {'baseColorTexture': {'index': 0}, 'metallicFactor': 0.0,
+                                                                          'roughnessFactor': 1.0}}]}
+    else:
+        extras = {}
+    if not rigged:
+        doc = {'asset': {'version': '2.0', 'generator': GENERATOR}, 'scene': 0, 'scenes': [{'nodes': [0]}],
+               'nodes': [{'name': 'body', 'mesh': 0}], 'meshes': [mesh], **extras}
+        return _finish(path, doc, buf)
 
     g = np.asarray(cnl_gtfms, dtype=np.float32).astype(np.float64).reshape(N_JOINTS, 4, 4)
     ibm = np.stack([np.linalg.inv(g[b]).T for b in range(N_JOINTS)]).astype('<f4')                  # column-major
@@ -144,7 +197,7 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
     skin = {'joints': list(range(first, first + N_JOINTS)), 'skeleton': first, 'name': 'smpl',
             'inverseBindMatrices': buf.add(ibm.reshape(N_JOINTS, 16), FLOAT, 'MAT4')}
     doc = {'asset': {'version': '2.0', 'generator': GENERATOR}, 'scene': 0, 'scenes': [{'nodes': [0, top]}], 'nodes': nodes,
-           'meshes': [mesh], 'skins': [skin]}
+           'meshes': [mesh], 'skins': [skin], **extras}
 
     if animation is not None:
         rot = np.asarray(animation['rotation'], dtype=np.float64).reshape(F, N_JOINTS, 4)
@@ -164,7 +217,11 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
         if correctives is not None:
             channel(0, 'weights', np.eye(F).reshape(F * F), 'SCALAR', 'STEP')
         doc['animations'] = [{'name': 'capture', 'samplers': samplers, 'channels': channels}]
+    return _finish(path, doc, buf)
 
+
+def _finish(path, doc, buf):
+    """The document and its buffer as the two chunks of <path> -> the number of bytes written."""
     buf.blob.extend(b'\0' * (-len(buf.blob) % 4))
     doc['buffers'] = [{'byteLength': len(buf.blob)}]
     doc['bufferViews'], doc['accessors'] = buf.views, buf.accessors

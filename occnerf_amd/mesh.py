@@ -20,11 +20,16 @@ counterpart there.
   skin_mesh, rig_frames, export_rig
                  the mesh as a rig (mesh_rig.enable): skin weights read off the motion-weight volume and
                  forward linear blend skinning in HIP (csrc/mesh_rig.hip), the frames' joint transforms as keys of one
-                 animation, rigged.glb (occnerf_amd/gltf.py) and rig.json.
+                 animation, rigged.glb (occnerf_amd/gltf.py) and rig.json;
+  atlas_layout, texture_uv, bake_texture, export_texture
+                 the mesh's colour as a texture (mesh_texture.enable): a per-triangle atlas whose texels
+                 are canonical points (csrc/mesh_texture.hip), coloured by Network.query_canonical -> texture.png, texture.json
+                 and the image inside rigged.glb or a static textured.glb.
 
 Every step is a pure function of its inputs: the same checkpoint and settings give the same PLY byte for byte (the sidecars
-differ in their wall times only).  Decimation, smoothing, hole filling, OBJ and a mesh welded from the f16x3 kernels' field
-are not offered; nor, for the posed mesh, roots of the warp other than the owning bone's or changes of topology."""
+differ in their wall times only).  Decimation, smoothing, hole filling, OBJ, a mesh welded from the f16x3 kernels' field,
+area-proportional or merged texture charts, mip-safe padding and normal maps are not offered; nor, for the posed mesh, roots of
+the warp other than the owning bone's or changes of topology."""
 import json
 import math
 import os
@@ -498,13 +503,16 @@ def _spread(d):
     return {'vertices': int(d.size), 'mean': float(d.mean()), 'p99': float(np.percentile(d, 99)), 'max': float(d.max())}
 
 
-def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, normals=True, iter_val=1e7):
+def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, normals=True, iter_val=1e7,
+               texture=None):
     """<out_dir>/rigged.glb and rig.json -> the sidecar's dict: the kept mesh of export_mesh(keep=...) with a skeleton, skin
     weights (skin_mesh) and, for rig['frames'] of `source` (a PoseFrames), the capture's motion as one animation (rig_frames).
     rig: the mesh_rig keys (RIG_DEFAULTS).  No frames: the rigged rest pose.  Per animated frame rig.json holds how far the
     rig's linear blend skinning (ops.mesh_lbs) is from the model's own posed mesh (pose_mesh with candidates / max_iter / tol /
     non_rigid, over its converged vertices); rig['correctives'] stores that difference as one morph target per frame, so that
-    at its key time the file shows the model's mesh.  rig['world']: a node above the root carries R(Rh), Th."""
+    at its key time the file shows the model's mesh.  rig['world']: a node above the root carries R(Rh), Th.  texture: None or
+    what export_texture left in kept['texture']: the file carries the atlas instead of COLOR_0, its primitive unwelded (DESIGN.md
+    section 7o), and rig.json gains 'textured' and 'unwelded_vertices'."""
     from . import gltf
     rig = check_rig(RIG_DEFAULTS if rig is None else rig)
     dev = net.point_base.device
@@ -564,7 +572,8 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
         normals=vertex_normals(v, faces) if normals else None,
         animation={'rotation': keys['rotation'], 'translation': keys['translation']} if F else None,
         world={'rotation': keys['world_rotation'], 'translation': keys['world_translation']} if F and rig['world'] else None,
-        correctives=delta.cpu().numpy() if correct and F else None, fps=float(rig['fps']))
+        correctives=delta.cpu().numpy() if correct and F else None, fps=float(rig['fps']),
+        **({} if texture is None else {'texture': {'uv': texture['uv'], 'png': texture['png']}}))
     t4 = time.perf_counter()
     n, share = count.cpu().numpy(), kept_share.cpu().numpy().astype(np.float64)
     bound = share[n > 0]
@@ -580,7 +589,126 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
             'non_rigid': bool(non_rigid and not net.cfg.ignore_non_rigid_motions), 'frames': per_frame,
             'seconds': {'keys': round(t1 - t0, 4), 'skin': round(t2 - t1, 4), 'pose': round(t_pose, 4), 'lbs': round(t_lbs, 4),
                         'report': round(t3 - t2 - t_pose - t_lbs, 4), 'write': round(t4 - t3, 4)}}
+    if texture is not None:
+        info.update(textured=True, unwelded_vertices=3 * int(len(faces)))
     with open(os.path.join(out_dir, 'rig.json'), 'w') as out:
         json.dump(info, out, indent=1)
         out.write('\n')
     return info
+
+
+# ------------------------------------------------------------------ the mesh's colour as a texture
+TEXTURE_DEFAULTS = {'enable': False, 'cell': 8, 'fill': [0, 0, 0]}
+
+
+def check_texture(texture):
+    """The mesh_texture keys as export_texture takes them (a dict with every key of TEXTURE_DEFAULTS); a value out of range is
+    refused by name."""
+    texture = {k: (texture.get(k, v) if hasattr(texture, 'get') else v) for k, v in TEXTURE_DEFAULTS.items()}
+    if not isinstance(texture['enable'], (bool, np.bool_)):
+        raise RuntimeError(f"mesh_texture.enable = {texture['enable']!r}: True or False")
+    cell = texture['cell']
+    if isinstance(cell, (bool, np.bool_)) or not isinstance(cell, (int, np.integer)) or \
+            not ops.MESH_TEXTURE_MIN_CELL <= int(cell) <= ops.MESH_TEXTURE_MAX_CELL:
+        raise RuntimeError(f'mesh_texture.cell = {cell!r}: a whole number of texels in {ops.MESH_TEXTURE_MIN_CELL}..'
+                           f'{ops.MESH_TEXTURE_MAX_CELL} (the edge of the cell two triangles share)')
+    fill = texture['fill']
+    if not (isinstance(fill, (list, tuple)) and len(fill) == 3 and all(
+            isinstance(c, (int, np.integer)) and not isinstance(c, (bool, np.bool_)) and 0 <= int(c) <= 255 for c in fill)):
+        raise RuntimeError(f'mesh_texture.fill = {fill!r}: three whole numbers in 0..255 (the colour of the texels no triangle owns)')
+    texture['cell'], texture['fill'] = int(cell), [int(c) for c in fill]
+    return texture
+
+
+def atlas_layout(T, n):
+    """(C, R, W, H, P) of the atlas of T triangles at cell edge n: triangles 2c and 2c + 1 share the n x n cell c at column
+    c % C, row c // C; C = ceil(sqrt(ceil(T / 2))), R = ceil(ceil(T / 2) / C), W = C n, H = R n, P = n (n - 1) / 2 texels per
+    triangle.  W or H above 16384, a cell outside 4..64 and an empty mesh are refused by name."""
+    return ops.mesh_texture_layout(T, n)
+
+
+def texture_uv(T, n):
+    """float32 [T,3,2]: per triangle and corner ((x + 0.5) / W, (y + 0.5) / H) of the texel that carries the corner, x / y the
+    atlas column / row; image row 0 is v = 0.  In the triangle's own frame the corners are the texels (0, 0), (m, 0), (0, m),
+    m = n - 3; an odd triangle's frame is the cell's, mirrored."""
+    C, _, W, H, _ = atlas_layout(T, n)
+    n, m = int(n), int(n) - 3
+    t = np.arange(int(T), dtype=np.int64)
+    own = np.array([[0, 0], [m, 0], [0, m]], dtype=np.int64)
+    inside = np.where((t & 1)[:, None, None] == 1, n - 1 - own[None], own[None])
+    cell = t >> 1
+    x = (cell % C)[:, None] * n + inside[..., 0]
+    y = (cell // C)[:, None] * n + inside[..., 1]
+    return np.stack([(x.astype(np.float64) + 0.5) / np.float64(W), (y.astype(np.float64) + 0.5) / np.float64(H)], -1).astype(np.float32)
+
+
+def bake_texture(net, verts, faces, n=8, fill=(0, 0, 0), chunk=1 << 21):
+    """(atlas uint8 [H,W,3] on the device, stats): the colour field on the per-triangle atlas of the mesh verts float32 [V,3]
+    (device) / faces int32 [T,3] (device or numpy): ops.mesh_texel_points, then sigmoid(Network.query_canonical(points)[:, :3])
+    in chunks of whole rows (rows are independent: any split gives the same bits), then ops.mesh_texture_fill into an atlas of
+    the colour `fill`.  A corner texel's point is its vertex, so its bytes are the vertex colour of mesh.ply."""
+    dev = verts.device
+    faces = torch.as_tensor(np.ascontiguousarray(np.asarray(faces, dtype=np.int32).reshape(-1, 3))).to(dev) \
+        if not torch.is_tensor(faces) else faces
+    T = int(faces.shape[0])
+    if T == 0 or int(verts.shape[0]) == 0:
+        raise RuntimeError(f'mesh_texture: the mesh has {int(verts.shape[0])} vertices and {T} triangles: there is nothing to bake '
+                           '(on a checkpoint without a surface at the default level set mesh.level)')
+    C, R, W, H, P = atlas_layout(T, n)
+
+    def clock():
+        torch.cuda.synchronize(dev)
+        return time.perf_counter()
+    t0 = clock()
+    pts = ops.mesh_texel_points(verts.detach().contiguous(), faces.contiguous(), int(n)).reshape(-1, 3)
+    t1 = clock()
+    rgb = torch.empty(T * P, 3, device=dev)
+    step = max(1, int(chunk))
+    for r0 in range(0, T * P, step):
+        rgb[r0:r0 + step] = torch.sigmoid(net.query_canonical(pts[r0:r0 + step].contiguous(), chunk=chunk)[:, :3])
+    t2 = clock()
+    atlas = torch.from_numpy(np.asarray(fill, dtype=np.uint8).reshape(3)).to(dev).expand(H, W, 3).contiguous()
+    ops.mesh_texture_fill(rgb, T, int(n), C, atlas)
+    t3 = clock()
+    return atlas, {'n': int(n), 'C': C, 'R': R, 'W': W, 'H': H, 'triangles': T, 'texels_queried': T * P,
+                   'unowned_share': 1.0 - float(T * P) / float(W * H),
+                   'bytes': {'points': T * P * 12, 'colours': T * P * 12, 'atlas': W * H * 3},
+                   'seconds': {'points': round(t1 - t0, 4), 'colour': round(t2 - t1, 4), 'fill': round(t3 - t2, 4)}}
+
+
+def export_texture(net, out_dir, kept, texture=None, chunk=1 << 21):
+    """<out_dir>/texture.png (through PIL, as image.py writes) and texture.json of the kept mesh of export_mesh(keep=...) -> the
+    sidecar's dict.  texture: the mesh_texture keys (TEXTURE_DEFAULTS).  kept receives 'texture': {'atlas': the device tensor,
+    'n', 'C', 'uv': texture_uv's, 'png': the bytes of texture.png}, what gltf.write_glb and mesh_view.export_views take."""
+    import io
+
+    from PIL import Image
+    texture = check_texture(TEXTURE_DEFAULTS if texture is None else texture)
+    verts, faces = kept['verts'], np.asarray(kept['faces'], dtype=np.int32).reshape(-1, 3)
+    n = int(texture['cell'])
+    atlas, info = bake_texture(net, verts, faces, n, texture['fill'], chunk)
+    t0 = time.perf_counter()
+    blob = io.BytesIO()
+    Image.fromarray(atlas.cpu().numpy()).save(blob, format='PNG')
+    png = blob.getvalue()
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'texture.png'), 'wb') as out:
+        out.write(png)
+    v = verts.cpu().numpy().astype(np.float64)
+    edge = np.concatenate([np.linalg.norm(v[faces[:, a]] - v[faces[:, b]], axis=1) for a, b in ((0, 1), (1, 2), (2, 0))])
+    info.update(fill=list(texture['fill']), texel_edge_m={'mean': float(edge.mean()) / (n - 3), 'max': float(edge.max()) / (n - 3)})
+    info['bytes']['png'] = len(png)
+    info['seconds']['write'] = round(time.perf_counter() - t0, 4)
+    kept['texture'] = {'atlas': atlas, 'n': n, 'C': info['C'], 'uv': texture_uv(len(faces), n), 'png': png}
+    with open(os.path.join(out_dir, 'texture.json'), 'w') as out:
+        json.dump(info, out, indent=1)
+        out.write('\n')
+    return info
+
+
+def export_textured(out_dir, kept, normals=True):
+    """<out_dir>/textured.glb: the kept mesh with its texture (export_texture has run) as a static glTF binary -> its size."""
+    from . import gltf
+    v, faces, tex = kept['verts'].cpu().numpy(), kept['faces'], kept['texture']
+    return gltf.write_glb(os.path.join(out_dir, 'textured.glb'), v, faces, None, None, None, None,
+                          normals=vertex_normals(v, faces) if normals else None, texture={'uv': tex['uv'], 'png': tex['png']})

@@ -13,8 +13,8 @@ with mesh_view.frames; DESIGN.md section 7j).  The reference draws no geometry; 
                  and body-space E -> view/<frame name>.png, the mesh beside the photograph, and view.json.
 
 Not offered: clipping at the near plane (a triangle with a vertex nearer than a millimetre is dropped and counted),
-anti-aliasing, lighting and textures, a comparison of the silhouette with the *rendered* alpha map, and the all_cameras.pkl
-rig."""
+anti-aliasing, lighting and textures other than the baked atlas of mesh_texture.enable (one more panel), a comparison of the
+silhouette with the *rendered* alpha map, and the all_cameras.pkl rig."""
 import json
 import os
 import time
@@ -27,15 +27,20 @@ from . import ops
 COUNTS = ops.MESH_RASTER_COUNTS
 
 
-def rasterize(verts, faces, colors, K, E, H, W, bgcolor=(255, 255, 255), faces_checked=False):
+def rasterize(verts, faces, colors, K, E, H, W, bgcolor=(255, 255, 255), faces_checked=False, texture=None):
     """verts float32 [V,3], faces int32 [T,3] and colors uint8 [V,3] on one GPU; K 3x3 and E 4x4 (the camera seen from the space
     of verts) on the host; bgcolor 0..255 -> a dict of device tensors: xy int32 [V,2], z float64 [V], vflag uint8 [V], cover
     uint8 [H,W], tri int32 [H,W] (-1 where empty), depth float32 [H,W] (+inf where empty), rgb uint8 [H,W,3] and counts int32
-    [7] in the order COUNTS (triangles dropped per reason, triangles of the wide pass, pixels covered).  Nothing is read back."""
+    [7] in the order COUNTS (triangles dropped per reason, triangles of the wide pass, pixels covered).  Nothing is read back.
+    texture: None or a dict with 'atlas' uint8 [aH,aW,3] on the GPU, 'n' and 'C' (mesh.export_texture's): the dict gains
+    'rgb_textured' uint8 [H,W,3], the same raster keys resolved through the atlas (ops.mesh_resolve_textured)."""
     xy, z, vflag = ops.mesh_project(verts, K, E)
     keys, counts = ops.mesh_raster(faces, xy, z, vflag, H, W, faces_checked=faces_checked)
     cover, tri, depth, rgb = ops.mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor)
-    return {'xy': xy, 'z': z, 'vflag': vflag, 'cover': cover, 'tri': tri, 'depth': depth, 'rgb': rgb, 'counts': counts}
+    out = {'xy': xy, 'z': z, 'vflag': vflag, 'cover': cover, 'tri': tri, 'depth': depth, 'rgb': rgb, 'counts': counts}
+    if texture is not None:
+        out['rgb_textured'] = ops.mesh_resolve_textured(keys, faces, xy, z, texture['atlas'], texture['n'], texture['C'], bgcolor)
+    return out
 
 
 def silhouette_iou(cover, gt_alpha):
@@ -48,10 +53,13 @@ def silhouette_iou(cover, gt_alpha):
 
 
 def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, panels=True,
-                 bgcolor=(255., 255., 255.), iter_val=1e7):
+                 bgcolor=(255., 255., 255.), iter_val=1e7, texture=None):
     """<out_dir>/view/<frame name>.png (panels: the mesh render beside the photograph) for the frames (indices into `dataset`,
     a dataset.PreparedDataset; 'all': every one) and <out_dir>/view.json -> its dict.  kept: what export_mesh(keep=...) left of
-    mesh.ply.  Every frame is posed here, in memory, as mesh.export_posed poses it (the same call, the same bits)."""
+    mesh.ply.  Every frame is posed here, in memory, as mesh.export_posed poses it (the same call, the same bits).  texture:
+    None or what mesh.export_texture left in kept['texture']: every view gets one more panel, the same raster keys resolved
+    through the atlas, and view.json per frame 'textured_mean_abs_diff', the mean absolute byte difference between that panel
+    and the vertex-colour one over the covered pixels (None when nothing is covered): reported, not judged."""
     from .image import ImageWriter
     from .mesh import _POSE_KEYS, pose_mesh
     if dataset is None:
@@ -85,7 +93,7 @@ def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20,
         stats = {}
         p, flag, _, _ = pose_mesh(net, verts, data, candidates, max_iter, tol, non_rigid, iter_val, stats)
         t0 = clock()
-        r = rasterize(p, faces, colors, f['K'], f['E'], H, W, bgcolor, faces_checked=True)
+        r = rasterize(p, faces, colors, f['K'], f['E'], H, W, bgcolor, faces_checked=True, texture=texture)
         t1 = clock()
         gt = torch.from_numpy(np.ascontiguousarray(dataset.gt_alpha(i))).to(dev)
         inter, union, iou, covered, inside = silhouette_iou(r['cover'], gt)
@@ -94,12 +102,16 @@ def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20,
         t2 = clock()
         if writer is not None:
             truth = torch.from_numpy(np.ascontiguousarray(dataset.truth_u8(i))).to(dev)
-            writer.append_device(torch.cat([r['rgb'], truth], dim=1), img_name=f['frame_name'])
+            writer.append_device(torch.cat([r['rgb']] + ([r['rgb_textured']] if texture is not None else []) + [truth], dim=1),
+                                 img_name=f['frame_name'])
         stats['seconds'].update(raster=round(t1 - t0, 4), compare=round(t2 - t1, 4))
         per_frame.append({'frame': i, 'name': f['frame_name'], 'iou': iou, 'intersection': inter, 'union': union,
                           'covered': covered, 'inside_share': inside,
                           'dropped': dict(zip(COUNTS[:5], counts[:5])), 'wide': counts[5], 'posing_flagged': flagged,
                           'seconds': stats['seconds']})
+        if texture is not None:
+            diff = (r['rgb_textured'].int() - r['rgb'].int()).abs()[r['cover'] > 0]
+            per_frame[-1]['textured_mean_abs_diff'] = float(diff.double().mean().item()) if covered else None
     if writer is not None:
         writer.finalize()
     ious = [f['iou'] for f in per_frame if f['iou'] is not None]

@@ -6,6 +6,7 @@ RuntimeError), allocates outputs with torch, and launches on torch's current str
 the tensors' device.  PyTorch is plumbing here: memory, streams, device guard.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -1752,6 +1753,124 @@ def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
                                              tri.data_ptr(), depth.data_ptr(), rgb.data_ptr(), pn, _stream(faces))
     _lib.check(rc, 'mesh_resolve')
     return cover, tri, depth, rgb
+
+
+# ------------------------------------------------------------------ the texture of the exported mesh
+MESH_TEXTURE_MIN_CELL, MESH_TEXTURE_MAX_CELL, MESH_TEXTURE_MAX_SIDE = 4, 64, 16384
+
+
+def mesh_texture_layout(T, n, who='mesh_texture'):
+    """(C, R, W, H, P) of the per-triangle atlas of T >= 1 triangles at cell edge n (4..64): ceil(T / 2) cells of n x n texels,
+    C = ceil(sqrt(cells)) per row, R rows, W = C n, H = R n, P = n (n - 1) / 2 texels per triangle.  A cell edge out of range,
+    T < 1 and W or H above 16384 are refused by name."""
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or \
+            not MESH_TEXTURE_MIN_CELL <= int(n) <= MESH_TEXTURE_MAX_CELL:
+        raise RuntimeError(f'{who}: cell = {n!r} is not a whole number in {MESH_TEXTURE_MIN_CELL}..{MESH_TEXTURE_MAX_CELL}')
+    T, n = int(T), int(n)
+    if T < 1:
+        raise RuntimeError(f'{who}: T = {T}: a mesh without triangles has no atlas')
+    cells = (T + 1) // 2
+    C = math.isqrt(cells - 1) + 1
+    R = (cells + C - 1) // C
+    W, H = C * n, R * n
+    if W > MESH_TEXTURE_MAX_SIDE or H > MESH_TEXTURE_MAX_SIDE:
+        raise RuntimeError(f'{who}: an atlas of {W} x {H} texels for {T} triangles at cell {n} exceeds {MESH_TEXTURE_MAX_SIDE} '
+                           '(lower mesh_texture.cell or mesh.resolution)')
+    return C, R, W, H, n * (n - 1) // 2
+
+
+def _mesh_texture_cell(who, n):
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or \
+            not MESH_TEXTURE_MIN_CELL <= int(n) <= MESH_TEXTURE_MAX_CELL:
+        raise RuntimeError(f'{who}: cell = {n!r} is not a whole number in {MESH_TEXTURE_MIN_CELL}..{MESH_TEXTURE_MAX_CELL}')
+    return int(n)
+
+
+def mesh_texel_points(verts, faces, n):
+    """The canonical points of the atlas' texels (occnerf_mesh_texel_points): verts float32 [V,3], faces int32 [T,3], n the cell
+    edge -> pts float32 [T,P,3], P = n (n - 1) / 2, on the device of verts.  A face index outside [0, V) is refused by name
+    after one blocking read of the kernel's status word (the kernel itself never uses one as an address).  T = 0 launches
+    nothing."""
+    n = _mesh_texture_cell('mesh_texel_points', n)
+    pv = _chk(verts, torch.float32, 'mesh_texel_points: verts')
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise RuntimeError(f'mesh_texel_points: verts must be float32 [V,3], got {tuple(verts.shape)}')
+    pf = _chk(faces, torch.int32, 'mesh_texel_points: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise RuntimeError(f'mesh_texel_points: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
+    V, T, P, dev = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2, verts.device
+    if V >= 1 << 31 or T * P >= 1 << 31:
+        raise RuntimeError(f'mesh_texel_points: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
+    pts = torch.empty(T, P, 3, device=dev, dtype=torch.float32)
+    if T == 0:
+        return pts
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _guard(verts):
+        rc = _lib.lib().occnerf_mesh_texel_points(pv, V, pf, T, n, pts.data_ptr(), status.data_ptr(), _stream(verts))
+    _lib.check(rc, 'mesh_texel_points')
+    if int(status.item()) != 0:
+        raise RuntimeError(f'mesh_texel_points: a face index lies outside [0, {V})')
+    return pts
+
+
+def _mesh_texture_atlas(who, atlas, T, n, C, dev):
+    pa = _chk(atlas, torch.uint8, f'{who}: atlas')
+    if atlas.dim() != 3 or atlas.shape[2] != 3 or atlas.device != dev:
+        raise RuntimeError(f'{who}: atlas must be uint8 [H,W,3] on the device of the other tensors, got {tuple(atlas.shape)}')
+    H, W, C = int(atlas.shape[0]), int(atlas.shape[1]), int(C)
+    rows = (((T + 1) // 2) + C - 1) // C if C >= 1 else 0
+    if C < 1 or W != C * n or rows * n > H or H > MESH_TEXTURE_MAX_SIDE or W > MESH_TEXTURE_MAX_SIDE:
+        raise RuntimeError(f'{who}: an atlas of H = {H}, W = {W} with C = {C} cells of {n} per row does not hold T = {T} triangles '
+                           f'(W = C n, {rows} rows of cells, at most {MESH_TEXTURE_MAX_SIDE} texels a side)')
+    return pa, H, W, C
+
+
+def mesh_texture_fill(rgb, T, n, C, atlas):
+    """The queried colours as bytes at their places in the atlas (occnerf_mesh_texture_fill): rgb float32 [T P,3] in the order
+    of mesh_texel_points' rows, atlas uint8 [H,W,3] with W = C n, filled by the caller, written IN PLACE -> atlas.  Only owned
+    texels are written: image.to_8b_image's rule, 0 for a NaN.  T = 0 launches nothing."""
+    n = _mesh_texture_cell('mesh_texture_fill', n)
+    pr = _chk(rgb, torch.float32, 'mesh_texture_fill: rgb')
+    T, P = int(T), n * (n - 1) // 2
+    if T < 0 or T * P >= 1 << 31 or tuple(rgb.shape) != (T * P, 3):
+        raise RuntimeError(f'mesh_texture_fill: rgb must be float32 [{T} x {P},3] with T P < 2^31, got {tuple(rgb.shape)}')
+    pa, H, W, C = _mesh_texture_atlas('mesh_texture_fill', atlas, T, n, C, rgb.device)
+    if T == 0:
+        return atlas
+    with _guard(rgb):
+        rc = _lib.lib().occnerf_mesh_texture_fill(pr, T, n, C, H, W, pa, _stream(rgb))
+    _lib.check(rc, 'mesh_texture_fill')
+    return atlas
+
+
+def mesh_resolve_textured(keys, faces, xy, z, atlas, n, C, bgcolor):
+    """The textured image of mesh_raster's keys (occnerf_mesh_resolve_textured), the twin of mesh_resolve: keys int64 [H,W],
+    faces int32 [T,3], mesh_project's xy / z, atlas uint8 [aH,aW,3] of cell edge n with C cells per row, bgcolor 3 values
+    0..255 on the host -> rgb uint8 [H,W,3].  The winner's four taps are its own texels.  No triangle: the background."""
+    n = _mesh_texture_cell('mesh_resolve_textured', n)
+    pk = _chk(keys, torch.int64, 'mesh_resolve_textured: keys')
+    if keys.dim() != 2:
+        raise RuntimeError(f'mesh_resolve_textured: keys must be int64 [H,W], got {tuple(keys.shape)}')
+    H, W = (int(s) for s in keys.shape)
+    pf = _chk(faces, torch.int32, 'mesh_resolve_textured: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise RuntimeError(f'mesh_resolve_textured: faces must be int32 [T,3], got {tuple(faces.shape)}')
+    px, pz = _chk(xy, torch.int32, 'mesh_resolve_textured: xy'), _chk(z, torch.float64, 'mesh_resolve_textured: z')
+    V, T, dev = int(z.numel()), int(faces.shape[0]), faces.device
+    if tuple(xy.shape) != (V, 2) or z.dim() != 1 or not (xy.device == z.device == keys.device == dev):
+        raise RuntimeError('mesh_resolve_textured: xy [V,2] and z [V] must be mesh_project\'s, keys mesh_raster\'s, on the device of faces')
+    if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE and H * W <= MESH_RASTER_MAX_PIXELS):
+        raise RuntimeError(f'mesh_resolve_textured: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE} or more than 2^28 pixels')
+    if T >= 1 << 31 or V >= 1 << 31:
+        raise RuntimeError(f'mesh_resolve_textured: T = {T} / V = {V} reaches the limit of 2^31')
+    pa, aH, aW, C = _mesh_texture_atlas('mesh_resolve_textured', atlas, T, n, C, dev)
+    bg = np.ascontiguousarray(np.clip(np.rint(np.asarray(bgcolor, dtype=np.float64).reshape(3)), 0, 255).astype(np.uint8))
+    rgb = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    with _guard(faces):
+        rc = _lib.lib().occnerf_mesh_resolve_textured(pk, pf, T, V, px, pz, H, W, pa, aH, aW, n, C, bg.ctypes.data,
+                                                      rgb.data_ptr(), _stream(faces))
+    _lib.check(rc, 'mesh_resolve_textured')
+    return rgb
 
 
 # ------------------------------------------------------------------ geometry maps of a rendered frame (DESIGN.md section 7k)

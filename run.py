@@ -7,7 +7,8 @@ exactly like the reference (run.py:79-81, image_util.py:53-75).  `load_net: seed
 seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on disk.  `--type mesh` writes no frames but
 <...>/<load_net>/mesh/mesh.ply and mesh.json; with `mesh_pose.frames` also mesh/posed/<frame name>.ply and mesh/posed.json;
 with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json; with `mesh_rig.enable True`
-also mesh/rigged.glb, the mesh with a skeleton, skin weights and the motion of `mesh_rig.frames`, and mesh/rig.json (run_mesh below).
+also mesh/rigged.glb, the mesh with a skeleton, skin weights and the motion of `mesh_rig.frames`, and mesh/rig.json; with
+`mesh_texture.enable True` also mesh/texture.png, the model's colour on a per-triangle atlas of the mesh (run_mesh below).
 `show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
 `geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
 `--type animate animate.motion PATH` drives the subject of a prepared dataset with a motion it has not seen (occnerf_amd/
@@ -285,8 +286,11 @@ def run_mesh():
     the silhouette's IoU against the frame's mask.  With mesh_rig.enable, also the kept mesh as a rigged glTF binary (occnerf_amd/
     mesh.py export_rig) -> mesh/rigged.glb: 24 SMPL joints, skin weights from the motion-weight volume, the
     frames mesh_rig.frames of the movement source as one animation (none: the rest pose), with mesh_rig.correctives a morph
-    target per frame that closes the gap to the model's own posed mesh; mesh/rig.json says how large that gap is.  Rank 0 alone
-    works."""
+    target per frame that closes the gap to the model's own posed mesh; mesh/rig.json says how large that gap is.  With
+    mesh_texture.enable, also the model's colour baked into a per-triangle atlas of the kept mesh (occnerf_amd/mesh.py
+    export_texture) -> mesh/texture.png and texture.json; the image replaces the vertex colours in
+    rigged.glb, without the rig it goes into a static mesh/textured.glb, and every mesh_view panel gains a textured render.
+    Rank 0 alone works."""
     from occnerf_amd.mesh import PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
     cfg.ignore_non_rigid_motions = True
@@ -312,7 +316,12 @@ def run_mesh():
         if rigging:
             from occnerf_amd.mesh import check_rig
             mrig = check_rig(mrig)
-        kept = {} if posing or viewing or rigging else None
+        mtex = cfg.get('mesh_texture') or {}
+        texturing = bool(mtex.get('enable', False))
+        if texturing:
+            from occnerf_amd.mesh import check_texture
+            mtex = check_texture(mtex)
+        kept = {} if posing or viewing or rigging or texturing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
                            normals=bool(m.normals), chunk=int(m.chunk), keep=kept, components=m.get('components', 'all'),
                            drop_cavities=m.get('drop_cavities', False))
@@ -322,6 +331,15 @@ def run_mesh():
             c = info['components']
             print(f"mesh: {c['kept']} of {c['found']} components kept ({c['passes']} labelling passes): {c['dropped_vertices']} "
                   f"vertices and {c['dropped_triangles']} triangles dropped, {c['cavities_dropped']} of the components as cavities")
+        if texturing:
+            # the colour field baked into a per-triangle atlas of the kept mesh
+            from occnerf_amd.mesh import export_texture, export_textured
+            tex = export_texture(model, out_dir, kept, mtex, chunk=int(m.chunk))
+            print(f"texture: {tex['texels_queried']} texels of {tex['triangles']} triangles in cells of {tex['n']} -> "
+                  f"{os.path.join(out_dir, 'texture.png')} ({tex['W']} x {tex['H']}, {100.0 * tex['unowned_share']:.1f} % unowned)")
+            if not rigging:
+                size = export_textured(out_dir, kept, normals=bool(m.normals))
+                print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
         if posing:
             # the mesh in the pose of frames of the movement source: its body constants only
             cfg.ignore_non_rigid_motions = ignore_non_rigid
@@ -341,7 +359,8 @@ def run_mesh():
                                 bbox_offset=float(cfg.bbox_offset), volume_size=int(cfg.mweight_volume.volume_size))
             rigged = export_rig(model, out_dir, kept, source, mrig, candidates=int(mp.get('candidates', 3)),
                                 max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
-                                non_rigid=bool(mp.get('non_rigid', True)), normals=bool(m.normals), iter_val=cfg.eval_iter)
+                                non_rigid=bool(mp.get('non_rigid', True)), normals=bool(m.normals), iter_val=cfg.eval_iter,
+                                **({'texture': kept['texture']} if texturing else {}))
             print(f"rig: {rigged['vertices']} vertices with up to {rigged['K']} joints each ({rigged['bound_to_root_for_want_of_a_bone']} "
                   f"bound to the root for want of a bone), {len(rigged['frames'])} keys -> {os.path.join(out_dir, 'rigged.glb')} "
                   f"({rigged['bytes']} bytes)")
@@ -361,7 +380,8 @@ def run_mesh():
             views = export_views(model, out_dir, kept, dataset, mv.frames, candidates=int(mp.get('candidates', 3)),
                                  max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
                                  non_rigid=bool(mp.get('non_rigid', True)), panels=bool(mv.get('panels', True)),
-                                 bgcolor=cfg.bgcolor, iter_val=cfg.eval_iter)
+                                 bgcolor=cfg.bgcolor, iter_val=cfg.eval_iter,
+                                 **({'texture': kept['texture']} if texturing else {}))
             for f in views['frames']:
                 iou = 'none (empty union)' if f['iou'] is None else f"{f['iou']:.4f}"
                 print(f"view {f['name']}: IoU {iou} ({f['intersection']} / {f['union']} pixels), {f['covered']} pixels covered, "
