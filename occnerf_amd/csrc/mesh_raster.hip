@@ -17,8 +17,10 @@
 //
 // Coverage is int64 arithmetic on the fixed-point coordinates; the fp64 steps use + * / rint and comparisons only, one rounding
 // per operator in the order of tests/mesh_raster_restatement.py (the tree is built with -ffp-contract=off): the outputs are that
-// file's, bit for bit.  Every index read from faces or from a key is checked before it is used as an address.
+// file's, bit for bit.  Every index read from faces or from a key is checked before it is used as an address.  The empty key, the
+// image-size test, the background and the byte store are mesh_screen.h's, shared with mesh_texture.hip's textured resolve.
 #include "common.h"
+#include "mesh_screen.h"
 
 namespace occ {
 
@@ -30,7 +32,6 @@ constexpr double kRasterFar = 1048576.0;          // 2^20
 constexpr double kRasterGuard = 4194304.0;        // 2^22 fixed-point units
 constexpr int kRasterMaxSide = 16384;
 constexpr int64_t kRasterMaxPixels = 1ll << 28;
-constexpr unsigned long long kRasterEmpty = ~0ull;
 enum RasterCount : int { kCntIndex = 0, kCntNear, kCntGuard, kCntArea, kCntOffscreen, kCntWide, kCntCovered, kCntTotal };
 
 struct RasterCamera {
@@ -190,10 +191,6 @@ __global__ __launch_bounds__(kRasterThreads) void mesh_raster_wide_kernel(
     }
 }
 
-struct RasterBg {
-    uint8_t c[3];
-};
-
 __global__ __launch_bounds__(kRasterThreads) void mesh_resolve_kernel(
     const unsigned long long *__restrict__ keys, const int32_t *__restrict__ faces, int64_t T, int64_t V,
     const int32_t *__restrict__ xy, const uint8_t *__restrict__ vflag, const double *__restrict__ z,
@@ -219,8 +216,7 @@ __global__ __launch_bounds__(kRasterThreads) void mesh_resolve_kernel(
             for (int c = 0; c < 3; c++) {
                 const double s = (w0 * (double)colors[(int64_t)tr.v[0] * 3 + c] + w1 * (double)colors[(int64_t)tr.v[1] * 3 + c]) +
                                  w2 * (double)colors[(int64_t)tr.v[2] * 3 + c];
-                const double r = rint(s);
-                out[c] = (uint8_t)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);      // (a NaN cannot arise: iz > 0)
+                out[c] = raster_byte(s);      // (a NaN cannot arise: iz > 0)
             }
         }
         cover[pix] = hit ? 1 : 0;
@@ -232,7 +228,7 @@ __global__ __launch_bounds__(kRasterThreads) void mesh_resolve_kernel(
     raster_count(hit, counts + kCntCovered);
 }
 
-inline bool raster_size_ok(int32_t H, int32_t W) {
+bool raster_size_ok(int32_t H, int32_t W) {
     return H >= 1 && W >= 1 && H <= kRasterMaxSide && W <= kRasterMaxSide && (int64_t)H * W <= kRasterMaxPixels;
 }
 

@@ -12,8 +12,10 @@
 // tests/mesh_texture_restatement.py (the tree is built with -ffp-contract=off); the fill's product is the float32 one of
 // image.to_8b_image.  No atomics; every output is a pure function of the inputs: the same bytes on every run.  Every index read
 // from faces or from a key is checked before it is used as an address, and every atlas address lies inside the C x R cells the
-// entry has checked against the atlas' size.
+// entry has checked against the atlas' size.  The empty key, the image-size test, the background and the byte store are
+// mesh_screen.h's, shared with mesh_raster.hip's resolve.
 #include "common.h"
+#include "mesh_screen.h"
 
 namespace occ {
 
@@ -21,7 +23,6 @@ constexpr int kTexThreads = 256;
 constexpr int kTexMinCell = 4;
 constexpr int kTexMaxCell = 64;
 constexpr int kTexMaxSide = 16384;
-constexpr unsigned long long kTexEmpty = ~0ull;
 
 // Texel k of a triangle -> (i', j') in its own frame: row j' holds the n - 1 - j' texels i' = 0 .. n - 2 - j'.
 __device__ __forceinline__ void texel_of(int k, int n, int &i, int &j) {
@@ -85,20 +86,16 @@ __global__ __launch_bounds__(kTexThreads) void mesh_texture_fill_kernel(const fl
     }
 }
 
-struct TexBg {
-    uint8_t c[3];
-};
-
 __global__ __launch_bounds__(kTexThreads) void mesh_resolve_textured_kernel(
     const unsigned long long *__restrict__ keys, const int32_t *__restrict__ faces, int64_t T, int64_t V,
     const int32_t *__restrict__ xy, const double *__restrict__ z, int H, int W, const uint8_t *__restrict__ atlas, int aW, int n,
-    int C, TexBg bg, uint8_t *__restrict__ rgb) {
+    int C, RasterBg bg, uint8_t *__restrict__ rgb) {
     const int64_t pix = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (pix >= (int64_t)H * W) return;
     uint8_t out[3] = {bg.c[0], bg.c[1], bg.c[2]};
     const unsigned long long key = keys[pix];
     const int64_t t = (int64_t)(key & 0xFFFFFFFFull);
-    if (key != kTexEmpty && t < T) {
+    if (key != kRasterEmpty && t < T) {
         const int32_t v0 = faces[t * 3], v1 = faces[t * 3 + 1], v2 = faces[t * 3 + 2];
         if (v0 >= 0 && v0 < V && v1 >= 0 && v1 < V && v2 >= 0 && v2 < V) {
             const int64_t X0 = xy[(int64_t)v0 * 2], Y0 = xy[(int64_t)v0 * 2 + 1];
@@ -142,8 +139,7 @@ __global__ __launch_bounds__(kTexThreads) void mesh_resolve_textured_kernel(
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     const double s = ((w00 * (double)c00[c] + w10 * (double)c10[c]) + w01 * (double)c01[c]) + w11 * (double)c11[c];
-                    const double r = rint(s);
-                    out[c] = (uint8_t)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
+                    out[c] = raster_byte(s);
                 }
             }
         }
@@ -199,7 +195,7 @@ OCC_API int occnerf_mesh_resolve_textured(const uint64_t *keys, const int32_t *f
                                           int32_t n, int32_t C, const uint8_t *h_bgcolor, uint8_t *rgb, void *stream) {
     using namespace occ;
     OCC_REQUIRE(h_bgcolor, "mesh_resolve_textured: null argument");
-    OCC_REQUIRE(Himg >= 1 && Wimg >= 1 && Himg <= 16384 && Wimg <= 16384 && (int64_t)Himg * Wimg <= (1ll << 28),
+    OCC_REQUIRE(raster_size_ok(Himg, Wimg),
                 "mesh_resolve_textured: H=%d W=%d outside 1..16384 or more than 2^28 pixels", Himg, Wimg);
     OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_resolve_textured: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
     OCC_REQUIRE(T >= 0 && T < (1ll << 31), "mesh_resolve_textured: T=%lld outside 0..2^31-1", (long long)T);
@@ -210,7 +206,7 @@ OCC_API int occnerf_mesh_resolve_textured(const uint64_t *keys, const int32_t *f
                     "not hold T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", aH, aW, C, n, (long long)T, kTexMaxSide);
         OCC_REQUIRE(faces && xy && z && atlas, "mesh_resolve_textured: null argument");
     }
-    TexBg bg;
+    RasterBg bg;
     for (int c = 0; c < 3; c++) bg.c[c] = h_bgcolor[c];
     const int64_t N = (int64_t)Himg * Wimg;
     const int64_t Tk = (T > 0 && V > 0) ? T : 0;      // no triangle: no key names one (t < 0 fails), the background everywhere

@@ -14,7 +14,7 @@ counterpart there.
   pose_mesh      the vertices in the pose of a frame: the frame's non-rigid offset undone by a fixed point
                  on the renderer's own kernel (Network.unoffset_canonical), then the skeletal warp inverted per vertex by a
                  damped Newton iteration in HIP (csrc/mesh_pose.hip) -- the model only knows the map from a frame to the
-                 canonical body;
+                 canonical body; MeshPoser: pose_mesh with its settings, every frame solved once for all the exports below;
   export_posed   posed/<frame name>.ply per frame -- the faces and colours of mesh.ply, the posed vertices, their normals --
                  and posed.json;
   skin_mesh, rig_frames, export_rig
@@ -42,6 +42,23 @@ import torch
 from . import ops
 from .image import to_8b_image
 from .synth import vertex_normals
+
+
+def _clock(dev):
+    """The wall time once the device has finished what was queued: every 'seconds' entry of the sidecars is a difference of two."""
+    torch.cuda.synchronize(dev)
+    return time.perf_counter()
+
+
+def _write_sidecar(path, info):
+    with open(path, 'w') as out:
+        json.dump(info, out, indent=1)
+        out.write('\n')
+
+
+def _normals(v, faces, normals):
+    """What write_ply and gltf.write_glb take as normals: None when not asked for, zeros for a mesh without triangles."""
+    return (vertex_normals(v, faces) if len(faces) else np.zeros_like(v)) if normals else None
 
 
 def grid_shape(bbox_min, bbox_max, resolution):
@@ -239,28 +256,24 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
     components, drop_cavities = check_components(components), check_drop_cavities(drop_cavities)
     cleaning = components != 'all' or drop_cavities
     dev = net.point_base.device
-
-    def clock():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    t0 = clock()
+    t0 = _clock(dev)
     field, h, (nx, ny, nz) = density_grid(net, bbox_min, bbox_max, resolution, chunk)
-    t1 = clock()
+    t1 = _clock(dev)
     used = default_level(h) if level is None else float(level)
     lo = np.asarray(bbox_min, dtype=np.float32).reshape(3).astype(np.float64)
     verts, faces = extract_mesh(field, used, lo, h)
     on_boundary = boundary_inside(field, used)
-    t2 = t_clean = clock()
+    t2 = t_clean = _clock(dev)
     if cleaning:
         extracted = (int(verts.shape[0]), int(faces.shape[0]))
         labels, records, passes = component_table(verts, faces, lo, h, (nx, ny, nz))
         verdicts = component_verdicts(records, components, drop_cavities)
         verts, faces = filter_mesh(verts, faces, labels, [v == 'kept' for v in verdicts])
         report = components_report(records, verdicts, components, drop_cavities, passes, h, lo)
-        t_clean = clock()
+        t_clean = _clock(dev)
     rgb = torch.sigmoid(net.query_canonical(verts, chunk=chunk)[:, :3])
     colors = to_8b_image(rgb.cpu().numpy())
-    t3 = clock()
+    t3 = _clock(dev)
     if on_boundary:
         warnings.warn(f'export_mesh: {on_boundary} grid points on the boundary of the box are inside the surface (density above '
                       f'{float(np.float32(used)):g}): the mesh is open there and is written as it is')
@@ -268,8 +281,7 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
     if keep is not None:
         keep.update(verts=verts, faces=f, colors=colors)
     os.makedirs(out_dir, exist_ok=True)
-    write_ply(os.path.join(out_dir, 'mesh.ply'), v, f, colors, vertex_normals(v, f) if normals and len(f) else
-              (np.zeros_like(v) if normals else None))
+    write_ply(os.path.join(out_dir, 'mesh.ply'), v, f, colors, _normals(v, f, normals))
     info = {'resolution': int(resolution), 'h': h, 'level': float(np.float32(used)), 'level_is_default': level is None,
             'grid_shape_xyz': [nx, ny, nz], 'vertices': int(v.shape[0]), 'triangles': int(f.shape[0]),
             'inside_points_on_boundary': on_boundary, 'normals': bool(normals),
@@ -277,39 +289,68 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
     if cleaning:
         info.update(extracted_vertices=extracted[0], extracted_triangles=extracted[1], components=report)
         info['seconds']['components'] = round(t_clean - t2, 4)
-    with open(os.path.join(out_dir, 'mesh.json'), 'w') as out:
-        json.dump(info, out, indent=1)
-        out.write('\n')
+    _write_sidecar(os.path.join(out_dir, 'mesh.json'), info)
     return info
 
 
 # ------------------------------------------------------------------ the mesh in the pose of a frame
-def pose_mesh(net, verts, data, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, iter_val=1e7, stats=None):
+def pose_mesh(net, verts, data, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, iter_val=1e7, stats=None, preamble=None):
     """(posed float32 [V,3], flag uint8 [V], iters uint8 [V], resid float32 [V]) on the device: where the frame `data` (the
     renderer's per-frame dict: dst_Rs, dst_Ts, dst_posevec, cnl_gtfms, motion_weights_priors as tensors, the box constants) puts
     the canonical vertices `verts`, in the body's own space -- the p the render of that frame maps onto the vertex: the
     non-rigid offset undone (Network.unoffset_canonical; non_rigid False: taken as absent), then ops.mesh_pose on the frame's
     Rs / Ts / motion-weight volume as Network.render_preamble computes them.  flag: 0 solved, 1 not converged, 2 no bone
-    carries the vertex.  stats: a dict that receives the rows the fixed point left moving and the wall times."""
+    carries the vertex.  stats: a dict that receives the rows the fixed point left moving and the wall times.  preamble: what
+    net.render_preamble(data, iter_val) returned, where the caller has it."""
     dev = net.point_base.device
-
-    def clock():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    t0 = clock()
-    Rs, Ts, vol = net.render_preamble(data, iter_val)
+    t0 = _clock(dev)
+    Rs, Ts, vol = preamble or net.render_preamble(data, iter_val)
     if non_rigid:
         s, moving = net.unoffset_canonical(verts, data, iter_val)
     else:
         s, moving = verts.detach().contiguous(), None
-    t1 = clock()
+    t1 = _clock(dev)
     out = ops.mesh_pose(s, Rs, Ts, vol[:Rs.shape[0]], ops.host_float3(data['cnl_bbox_min_xyz']),
                         ops.host_float3(data['cnl_bbox_scale_xyz']), candidates=candidates, max_iter=max_iter, tol=tol)
-    t2 = clock()
+    t2 = _clock(dev)
     if stats is not None:
         stats.update(non_rigid_moving=0 if moving is None else int(moving.sum().item()),
                      seconds={'unoffset': round(t1 - t0, 4), 'pose': round(t2 - t1, 4)})
     return out
+
+
+class MeshPoser:
+    """pose_mesh of one mesh's `verts` with its five settings, every frame solved once.  frame(key, data) -> (Rs, Ts, p, flag,
+    iters, resid, stats): the frame's backward bases and pose_mesh's result and stats from one Network.render_preamble call,
+    computed at the first call for `key` (the frame's index in its source: one poser serves one source) and kept on the device,
+    18 bytes per vertex and frame (keep False: nothing is kept, for an export that asks for every frame once); `solved`
+    counts the solves.  A pure function of the inputs: a kept result is the bytes a second solve would give.  The
+    motion-weight volume is not kept.  of(poser, ...): the poser an export was handed, refused when it is another mesh's,
+    or a new one."""
+
+    def __init__(self, net, verts, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, iter_val=1e7, keep=True):
+        self.net, self.verts, self.keep = net, verts, keep
+        self.candidates, self.max_iter, self.tol, self.non_rigid, self.iter_val = candidates, max_iter, tol, non_rigid, iter_val
+        self.solved, self._frames = 0, {}
+
+    @classmethod
+    def of(cls, poser, net, verts, *settings, keep=True):
+        if poser is not None and poser.verts is not verts:
+            raise RuntimeError("poser: a MeshPoser of other vertices than kept['verts']: its frames are another mesh's")
+        return poser or cls(net, verts, *settings, keep=keep)
+
+    def frame(self, key, data):
+        found = self._frames.get(key)
+        if found is None:
+            stats, pre = {}, self.net.render_preamble(data, self.iter_val)
+            posed = pose_mesh(self.net, self.verts, data, self.candidates, self.max_iter, self.tol, self.non_rigid, self.iter_val,
+                              stats, pre)
+            found = (*pre[:2], *posed, stats)
+            self.solved += 1
+            if self.keep:
+                self._frames[key] = found
+        *out, stats = found
+        return (*out, {**stats, 'seconds': dict(stats['seconds'])})         # the callers add their own wall times
 
 
 def to_world(p, Rh, Th):
@@ -372,37 +413,34 @@ def _device_frame(fr, dev):
 
 
 def export_posed(net, out_dir, kept, source, frames, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, world=False,
-                 normals=True, iter_val=1e7):
+                 normals=True, iter_val=1e7, poser=None):
     """<out_dir>/posed/<frame name>.ply for the frames (indices into `source`, a PoseFrames; 'all': every one) and
     <out_dir>/posed.json -> its dict.  kept: what export_mesh(keep=...) left of mesh.ply: every posed PLY has its faces and
-    colours, the posed vertices and (normals) the normals recomputed from them."""
+    colours, the posed vertices and (normals) the normals recomputed from them.  poser: a MeshPoser of kept['verts'] over
+    `source` to take the frames from (its settings replace candidates .. iter_val); None: one is built here."""
     dev = net.point_base.device
     idxs = _frame_indices(source, frames, 'mesh_pose.frames')
     verts, faces, colors = kept['verts'], kept['faces'], kept['colors']
+    poser = MeshPoser.of(poser, net, verts, candidates, max_iter, tol, non_rigid, iter_val, keep=False)
     os.makedirs(os.path.join(out_dir, 'posed'), exist_ok=True)
     V, per_frame = int(verts.shape[0]), []
     for i in idxs:
         name, fr, Rh, Th = source.frame(i)
-        data = _device_frame(fr, dev)
-        stats = {}
-        p, flag, iters, resid = pose_mesh(net, verts, data, candidates, max_iter, tol, non_rigid, iter_val, stats)
+        _, _, p, flag, iters, resid, stats = poser.frame(i, _device_frame(fr, dev))
         t0 = time.perf_counter()
         p, flag = p.cpu().numpy(), flag.cpu().numpy()
         if world:
             p = to_world(p, Rh, Th)
-        write_ply(os.path.join(out_dir, 'posed', f'{name}.ply'), p, faces, colors,
-                  vertex_normals(p, faces) if normals and len(faces) else (np.zeros_like(p) if normals else None))
+        write_ply(os.path.join(out_dir, 'posed', f'{name}.ply'), p, faces, colors, _normals(p, faces, normals))
         stats['seconds']['write'] = round(time.perf_counter() - t0, 4)
         counts = np.bincount(flag, minlength=3)
         per_frame.append({'frame': i, 'name': name, 'converged': int(counts[0]), 'not_converged': int(counts[1]),
                           'no_bone': int(counts[2]), 'flagged_share': float(counts[1] + counts[2]) / max(V, 1),
                           'worst_resid': float(resid.max().item()) if V else 0.0,
                           'mean_iters': float(iters.float().mean().item()) if V else 0.0, **stats})
-    info = {'vertices': V, 'candidates': int(candidates), 'max_iter': int(max_iter), 'tol': float(tol),
-            'non_rigid': bool(non_rigid and not net.cfg.ignore_non_rigid_motions), 'world': bool(world), 'frames': per_frame}
-    with open(os.path.join(out_dir, 'posed.json'), 'w') as out:
-        json.dump(info, out, indent=1)
-        out.write('\n')
+    info = {'vertices': V, 'candidates': int(poser.candidates), 'max_iter': int(poser.max_iter), 'tol': float(poser.tol),
+            'non_rigid': bool(poser.non_rigid and not net.cfg.ignore_non_rigid_motions), 'world': bool(world), 'frames': per_frame}
+    _write_sidecar(os.path.join(out_dir, 'posed.json'), info)
     return info
 
 
@@ -468,21 +506,22 @@ def local_keys(G, previous=None):
     return rot, tra
 
 
-def rig_frames(net, source, frames, iter_val=1e7):
+def rig_frames(net, source, frames, iter_val=1e7, poser=None):
     """The skeleton's keys for the frames (indices into `source`, a PoseFrames; 'all': every one) -> a dict: 'index', 'name',
     'data' (the frames' device constants) per frame; 'Rs' [F,nb,3,3] / 'Ts' [F,nb,3] on the device, the backward bases of
     Network.render_preamble with the pose refiner in them; 'G' [F,nb,4,4] float64, the global joint transforms
     inv([R_b | T_b]) cnl_gtfms_b; 'rotation' [F,nb,4] / 'translation' [F,nb,3] float64, the local transforms over
     synth.SMPL_PARENT as unit quaternions (Shepperd's branch; the sign of the non-negative dot product with the key before) and
     offsets -- the offset is written per key: it is the rest offset up to the float32 rounding inside Rs / Ts, and with it the
-    file reproduces G; 'world_rotation' [F,4] / 'world_translation' [F,3]: R(Rh) and Th, what to_world applies."""
+    file reproduces G; 'world_rotation' [F,4] / 'world_translation' [F,3]: R(Rh) and Th, what to_world applies.  poser: a
+    MeshPoser over `source` whose frames carry the Rs / Ts (the same bits); None: Network.render_preamble is called here."""
     from .gltf import quaternion
     dev = net.point_base.device
     out = {k: [] for k in ('index', 'name', 'data', 'Rs', 'Ts', 'G', 'rotation', 'translation', 'world_rotation', 'world_translation')}
     for i in _frame_indices(source, frames, 'mesh_rig.frames'):
         name, fr, Rh, Th = source.frame(i)
         data = _device_frame(fr, dev)
-        Rs, Ts, _ = net.render_preamble(data, iter_val)
+        Rs, Ts = (net.render_preamble(data, iter_val) if poser is None else poser.frame(i, data))[:2]
         G = joint_transforms(Rs.cpu().numpy(), Ts.cpu().numpy(), fr['cnl_gtfms'])
         rot, tra = local_keys(G, out['rotation'][-1] if out['rotation'] else None)
         wq = quaternion(np.asarray(Rh, dtype=np.float32).astype(np.float64), out['world_rotation'][-1] if out['world_rotation'] else None)
@@ -504,7 +543,7 @@ def _spread(d):
 
 
 def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, normals=True, iter_val=1e7,
-               texture=None):
+               texture=None, poser=None):
     """<out_dir>/rigged.glb and rig.json -> the sidecar's dict: the kept mesh of export_mesh(keep=...) with a skeleton, skin
     weights (skin_mesh) and, for rig['frames'] of `source` (a PoseFrames), the capture's motion as one animation (rig_frames).
     rig: the mesh_rig keys (RIG_DEFAULTS).  No frames: the rigged rest pose.  Per animated frame rig.json holds how far the
@@ -512,15 +551,13 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
     non_rigid, over its converged vertices); rig['correctives'] stores that difference as one morph target per frame, so that
     at its key time the file shows the model's mesh.  rig['world']: a node above the root carries R(Rh), Th.  texture: None or
     what export_texture left in kept['texture']: the file carries the atlas instead of COLOR_0, its primitive unwelded (DESIGN.md
-    section 7o), and rig.json gains 'textured' and 'unwelded_vertices'."""
+    section 7o), and rig.json gains 'textured' and 'unwelded_vertices'.  poser: as for export_posed; a frame it has solved is
+    not solved again, the others are where rig_frames asks for their Rs / Ts: seconds['keys'] holds those solves,
+    seconds['pose'] the fetching of their results."""
     from . import gltf
     rig = check_rig(RIG_DEFAULTS if rig is None else rig)
     dev = net.point_base.device
     K, correct = int(rig['influences']), bool(rig['correctives'])
-
-    def clock():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
     verts, faces, colors = kept['verts'], kept['faces'], kept['colors']
     V = int(verts.shape[0])
     if V == 0 or len(faces) == 0:
@@ -530,30 +567,29 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
     if correct and len(idxs) > int(rig['max_correctives']):
         raise RuntimeError(f"mesh_rig.correctives: {len(idxs)} frames are more than mesh_rig.max_correctives = "
                            f"{int(rig['max_correctives'])}: every frame adds a morph target of {V} x 12 bytes to the file")
-    t0 = clock()
-    keys = rig_frames(net, source, idxs, iter_val)
-    t1 = clock()
+    poser = MeshPoser.of(poser, net, verts, candidates, max_iter, tol, non_rigid, iter_val)
+    if not poser.keep:
+        raise RuntimeError('export_rig: a MeshPoser with keep=False would solve every frame twice, for its key and for its target')
+    t0 = _clock(dev)
+    keys = rig_frames(net, source, idxs, poser.iter_val, poser)
+    t1 = _clock(dev)
     fr0 = source.frame(idxs[0] if idxs else 0)[1]               # the subject's constants: any frame has them
     cnl, data0 = np.asarray(fr0['cnl_gtfms']), keys['data'][0] if idxs else _device_frame(fr0, dev)
-    joints, weights, count, kept_share = skin_mesh(net, verts, data0, K, iter_val)
-    t2 = clock()
+    joints, weights, count, kept_share = skin_mesh(net, verts, data0, K, poser.iter_val)
+    t2 = _clock(dev)
     F, per_frame, delta = len(idxs), [], None
     t_pose = t_lbs = 0.0
     if F:
-        targets, flags = [], []
-        for f in range(F):
-            ta = clock()
-            p, flag, _, _ = pose_mesh(net, verts, keys['data'][f], candidates, max_iter, tol, non_rigid, iter_val)
-            targets.append(p), flags.append(flag)
-            t_pose += clock() - ta
-        ta = clock()
-        target, tflag = torch.stack(targets).contiguous(), torch.stack(flags).contiguous()
+        ta = _clock(dev)
+        model = [poser.frame(i, data) for i, data in zip(idxs, keys['data'])]       # (solved when rig_frames asked for Rs / Ts)
+        tb = _clock(dev)
+        target, tflag = torch.stack([m[2] for m in model]).contiguous(), torch.stack([m[3] for m in model]).contiguous()
         x = verts.detach().contiguous()
         if correct:
             posed, delta, dflag = ops.mesh_lbs(x, joints, weights, keys['Rs'], keys['Ts'], target, tflag, float(rig['max_delta']))
         else:
             posed = ops.mesh_lbs(x, joints, weights, keys['Rs'], keys['Ts'])
-        t_lbs = clock() - ta
+        t_pose, t_lbs = tb - ta, _clock(dev) - tb
         rest = gltf.rest_translations(cnl)
         dist = (posed.double() - target.double()).norm(dim=2).cpu().numpy()
         solved = tflag.cpu().numpy() == 0
@@ -564,12 +600,12 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
                 row.update(corrective_flagged=int(dflag[f].sum().item()), corrective_stored=int(V - dflag[f].sum().item()),
                            corrective_max_m=float(delta[f].abs().max().item()))
             per_frame.append(row)
-    t3 = clock()
+    t3 = _clock(dev)
     v = verts.cpu().numpy()
     os.makedirs(out_dir, exist_ok=True)
     size = gltf.write_glb(
         os.path.join(out_dir, 'rigged.glb'), v, faces, colors, joints.cpu().numpy(), weights.cpu().numpy(), cnl,
-        normals=vertex_normals(v, faces) if normals else None,
+        normals=_normals(v, faces, normals),
         animation={'rotation': keys['rotation'], 'translation': keys['translation']} if F else None,
         world={'rotation': keys['world_rotation'], 'translation': keys['world_translation']} if F and rig['world'] else None,
         correctives=delta.cpu().numpy() if correct and F else None, fps=float(rig['fps']),
@@ -585,15 +621,13 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
             'axes': "the body's own space, as mesh.ply: x body left, y up, z front of the canonical body, metres; nothing is "
                     "rotated to glTF's +Y-up, +Z-front convention and nothing is rescaled",
             'correctives': correct, 'max_delta': float(rig['max_delta']), 'world': bool(rig['world']),
-            'candidates': int(candidates), 'max_iter': int(max_iter), 'tol': float(tol),
-            'non_rigid': bool(non_rigid and not net.cfg.ignore_non_rigid_motions), 'frames': per_frame,
+            'candidates': int(poser.candidates), 'max_iter': int(poser.max_iter), 'tol': float(poser.tol),
+            'non_rigid': bool(poser.non_rigid and not net.cfg.ignore_non_rigid_motions), 'frames': per_frame,
             'seconds': {'keys': round(t1 - t0, 4), 'skin': round(t2 - t1, 4), 'pose': round(t_pose, 4), 'lbs': round(t_lbs, 4),
                         'report': round(t3 - t2 - t_pose - t_lbs, 4), 'write': round(t4 - t3, 4)}}
     if texture is not None:
         info.update(textured=True, unwelded_vertices=3 * int(len(faces)))
-    with open(os.path.join(out_dir, 'rig.json'), 'w') as out:
-        json.dump(info, out, indent=1)
-        out.write('\n')
+    _write_sidecar(os.path.join(out_dir, 'rig.json'), info)
     return info
 
 
@@ -655,21 +689,17 @@ def bake_texture(net, verts, faces, n=8, fill=(0, 0, 0), chunk=1 << 21):
         raise RuntimeError(f'mesh_texture: the mesh has {int(verts.shape[0])} vertices and {T} triangles: there is nothing to bake '
                            '(on a checkpoint without a surface at the default level set mesh.level)')
     C, R, W, H, P = atlas_layout(T, n)
-
-    def clock():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
-    t0 = clock()
+    t0 = _clock(dev)
     pts = ops.mesh_texel_points(verts.detach().contiguous(), faces.contiguous(), int(n)).reshape(-1, 3)
-    t1 = clock()
+    t1 = _clock(dev)
     rgb = torch.empty(T * P, 3, device=dev)
     step = max(1, int(chunk))
     for r0 in range(0, T * P, step):
         rgb[r0:r0 + step] = torch.sigmoid(net.query_canonical(pts[r0:r0 + step].contiguous(), chunk=chunk)[:, :3])
-    t2 = clock()
+    t2 = _clock(dev)
     atlas = torch.from_numpy(np.asarray(fill, dtype=np.uint8).reshape(3)).to(dev).expand(H, W, 3).contiguous()
     ops.mesh_texture_fill(rgb, T, int(n), C, atlas)
-    t3 = clock()
+    t3 = _clock(dev)
     return atlas, {'n': int(n), 'C': C, 'R': R, 'W': W, 'H': H, 'triangles': T, 'texels_queried': T * P,
                    'unowned_share': 1.0 - float(T * P) / float(W * H),
                    'bytes': {'points': T * P * 12, 'colours': T * P * 12, 'atlas': W * H * 3},
@@ -700,9 +730,7 @@ def export_texture(net, out_dir, kept, texture=None, chunk=1 << 21):
     info['bytes']['png'] = len(png)
     info['seconds']['write'] = round(time.perf_counter() - t0, 4)
     kept['texture'] = {'atlas': atlas, 'n': n, 'C': info['C'], 'uv': texture_uv(len(faces), n), 'png': png}
-    with open(os.path.join(out_dir, 'texture.json'), 'w') as out:
-        json.dump(info, out, indent=1)
-        out.write('\n')
+    _write_sidecar(os.path.join(out_dir, 'texture.json'), info)
     return info
 
 
@@ -711,4 +739,4 @@ def export_textured(out_dir, kept, normals=True):
     from . import gltf
     v, faces, tex = kept['verts'].cpu().numpy(), kept['faces'], kept['texture']
     return gltf.write_glb(os.path.join(out_dir, 'textured.glb'), v, faces, None, None, None, None,
-                          normals=vertex_normals(v, faces) if normals else None, texture={'uv': tex['uv'], 'png': tex['png']})
+                          normals=_normals(v, faces, normals), texture={'uv': tex['uv'], 'png': tex['png']})

@@ -15,9 +15,7 @@ with mesh_view.frames; DESIGN.md section 7j).  The reference draws no geometry; 
 Not offered: clipping at the near plane (a triangle with a vertex nearer than a millimetre is dropped and counted),
 anti-aliasing, lighting and textures other than the baked atlas of mesh_texture.enable (one more panel), a comparison of the
 silhouette with the *rendered* alpha map, and the all_cameras.pkl rig."""
-import json
 import os
-import time
 
 import numpy as np
 import torch
@@ -53,24 +51,23 @@ def silhouette_iou(cover, gt_alpha):
 
 
 def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20, tol=1e-7, non_rigid=True, panels=True,
-                 bgcolor=(255., 255., 255.), iter_val=1e7, texture=None):
+                 bgcolor=(255., 255., 255.), iter_val=1e7, texture=None, poser=None):
     """<out_dir>/view/<frame name>.png (panels: the mesh render beside the photograph) for the frames (indices into `dataset`,
     a dataset.PreparedDataset; 'all': every one) and <out_dir>/view.json -> its dict.  kept: what export_mesh(keep=...) left of
     mesh.ply.  Every frame is posed here, in memory, as mesh.export_posed poses it (the same call, the same bits).  texture:
     None or what mesh.export_texture left in kept['texture']: every view gets one more panel, the same raster keys resolved
     through the atlas, and view.json per frame 'textured_mean_abs_diff', the mean absolute byte difference between that panel
-    and the vertex-colour one over the covered pixels (None when nothing is covered): reported, not judged."""
+    and the vertex-colour one over the covered pixels (None when nothing is covered): reported, not judged.  poser: a
+    mesh.MeshPoser of kept['verts'] over `dataset` (its settings replace candidates .. iter_val); None: one is built here."""
     from .image import ImageWriter
-    from .mesh import _POSE_KEYS, pose_mesh
+    from .mesh import MeshPoser, _clock, _device_frame, _frame_indices, _write_sidecar
     if dataset is None:
         raise RuntimeError('mesh_view.frames: the silhouette is held against the masks of a prepared dataset; the synthetic frame '
                            'source has none (set train.dataset_path or movement.dataset)')
     dev = net.point_base.device
-    idxs = list(range(len(dataset))) if isinstance(frames, str) and frames == 'all' else [int(i) for i in frames]
-    for i in idxs:
-        if not 0 <= i < len(dataset):
-            raise RuntimeError(f'mesh_view.frames: frame {i} outside the {len(dataset)} frames of the dataset')
+    idxs = _frame_indices(dataset, frames, 'mesh_view.frames')
     verts = kept['verts']
+    poser = MeshPoser.of(poser, net, verts, candidates, max_iter, tol, non_rigid, iter_val, keep=False)
     V, T = int(verts.shape[0]), int(np.asarray(kept['faces']).shape[0])
     f_host = np.ascontiguousarray(np.asarray(kept['faces'], dtype=np.int32).reshape(-1, 3))
     if T and (f_host.min() < 0 or f_host.max() >= V):
@@ -80,26 +77,18 @@ def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20,
     H, W = int(dataset.height), int(dataset.width)
     os.makedirs(out_dir, exist_ok=True)
     writer = ImageWriter(output_dir=out_dir, exp_name='view') if panels else None
-
-    def clock():
-        torch.cuda.synchronize(dev)
-        return time.perf_counter()
     per_frame = []
     for i in idxs:
         f = dataset.frames[i]
-        fr = dataset.host_constants(i)
-        data = {k: torch.from_numpy(np.ascontiguousarray(fr[k])).to(dev) for k in _POSE_KEYS}
-        data.update({k: np.asarray(fr[k], dtype=np.float32) for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz')})
-        stats = {}
-        p, flag, _, _ = pose_mesh(net, verts, data, candidates, max_iter, tol, non_rigid, iter_val, stats)
-        t0 = clock()
+        _, _, p, flag, _, _, stats = poser.frame(i, _device_frame(dataset.host_constants(i), dev))
+        t0 = _clock(dev)
         r = rasterize(p, faces, colors, f['K'], f['E'], H, W, bgcolor, faces_checked=True, texture=texture)
-        t1 = clock()
+        t1 = _clock(dev)
         gt = torch.from_numpy(np.ascontiguousarray(dataset.gt_alpha(i))).to(dev)
         inter, union, iou, covered, inside = silhouette_iou(r['cover'], gt)
         counts = r['counts'].tolist()
         flagged = int((flag != 0).sum().item())
-        t2 = clock()
+        t2 = _clock(dev)
         if writer is not None:
             truth = torch.from_numpy(np.ascontiguousarray(dataset.truth_u8(i))).to(dev)
             writer.append_device(torch.cat([r['rgb']] + ([r['rgb_textured']] if texture is not None else []) + [truth], dim=1),
@@ -117,7 +106,5 @@ def export_views(net, out_dir, kept, dataset, frames, candidates=3, max_iter=20,
     ious = [f['iou'] for f in per_frame if f['iou'] is not None]
     info = {'vertices': V, 'triangles': T, 'height': H, 'width': W, 'mask_threshold': 0.5,
             'mean_iou': float(np.mean(ious)) if ious else None, 'frames': per_frame}
-    with open(os.path.join(out_dir, 'view.json'), 'w') as out:
-        json.dump(info, out, indent=1)
-        out.write('\n')
+    _write_sidecar(os.path.join(out_dir, 'view.json'), info)
     return info

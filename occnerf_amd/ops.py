@@ -1365,6 +1365,19 @@ def _mesh_field(who, field):
     return ptr, nx, ny, nz
 
 
+def _mesh_points(name, x):
+    """The address of x, float32 [V,3] points on the GPU; `name`: the entry and the argument, for the refusal."""
+    ptr = _chk(x, torch.float32, name)
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise RuntimeError(f'{name} must be float32 [V,3], got {tuple(x.shape)}')
+    return ptr
+
+
+def _mesh_bgcolor(bgcolor):
+    """bgcolor, 3 values 0..255 on the host, as the uint8 [3] the resolves take: rounded to nearest, clamped."""
+    return np.ascontiguousarray(np.clip(np.rint(np.asarray(bgcolor, dtype=np.float64).reshape(3)), 0, 255).astype(np.uint8))
+
+
 def mesh_count(field, level):
     """Triangles of every row of cubes (z, y) of field [nz,ny,nx] float32 at the iso level (compared in float32; include/
     occnerf_hip.h occnerf_mesh_count) -> int32 [(nz-1)*(ny-1)] on the device.  Nothing is read back here."""
@@ -1474,9 +1487,7 @@ def mesh_component_stats(verts, faces, vrank, n_comp, bbox_min, h, shape):
     """The records of the n_comp = C components (occnerf_mesh_component_stats; include/occnerf_hip.h): verts float32 [V,3], faces int32
     [T,3], vrank int32 [V] (mesh_component_ranks), bbox_min[3] / h on the host, shape = (nx, ny, nz) of the grid -> (counts
     int32 [C,3]: vertices, triangles, boundary vertices; box int32 [C,6]: smin, smax; vol6 int64 [C]) on the device."""
-    pv = _chk(verts, torch.float32, 'mesh_component_stats: verts')
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise RuntimeError(f'mesh_component_stats: verts must be float32 [V,3], got {tuple(verts.shape)}')
+    pv = _mesh_points('mesh_component_stats: verts', verts)
     V, dev, n_comp = int(verts.shape[0]), verts.device, int(n_comp)
     pf, T = _mesh_faces('mesh_component_stats', faces, V, dev)
     pr = _chk(vrank, torch.int32, 'mesh_component_stats: vrank')
@@ -1524,9 +1535,7 @@ def mesh_pose(x_c, Rs, Ts, vol, bbox_min, bbox_scale, candidates=3, max_iter=20,
     Ts [nb,3] and vol [>= nb,G,G,G] (only the first nb channels are read: the background channel is dropped) as
     Network.render_preamble returns them, bbox_min[3] / bbox_scale[3] on the host -> (p float32 [V,3], flag uint8 [V],
     iters uint8 [V], resid float32 [V]) on the device of x_c.  V = 0 launches nothing."""
-    px = _chk(x_c, torch.float32, 'mesh_pose: x_c')
-    if x_c.dim() != 2 or x_c.shape[1] != 3:
-        raise RuntimeError(f'mesh_pose: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    px = _mesh_points('mesh_pose: x_c', x_c)
     pR, pT, pv = _chk(Rs, torch.float32, 'mesh_pose: Rs'), _chk(Ts, torch.float32, 'mesh_pose: Ts'), _chk(vol, torch.float32, 'mesh_pose: vol')
     nb = int(Rs.shape[0]) if Rs.dim() == 3 else -1
     if nb < 1 or tuple(Rs.shape) != (nb, 3, 3) or tuple(Ts.shape) != (nb, 3):
@@ -1564,9 +1573,7 @@ def mesh_skin(x_c, vol, bbox_min, bbox_scale, K=4):
     Network.render_preamble returns with the background channel dropped (vol[:nb], as mesh_pose reads it), bbox_min[3] / bbox_scale[3] on the host ->
     (joints uint8 [V,K], weights float32 [V,K], count uint8 [V], kept float32 [V]) on the device of x_c.  V = 0 launches
     nothing."""
-    px = _chk(x_c, torch.float32, 'mesh_skin: x_c')
-    if x_c.dim() != 2 or x_c.shape[1] != 3:
-        raise RuntimeError(f'mesh_skin: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    px = _mesh_points('mesh_skin: x_c', x_c)
     pv = _chk(vol, torch.float32, 'mesh_skin: vol')
     K = int(K)
     if K not in (4, 8):
@@ -1599,9 +1606,7 @@ def mesh_lbs(x_c, joints, weights, Rs, Ts, target=None, target_flag=None, max_de
     of the canonical vertex that makes its skinned position the target, 0 and flagged where it is not to be had or exceeds
     max_delta.  A joint index >= nb is refused by name before anything is launched (one blocking read of the joints' maximum;
     joints_checked=True: the caller has made that test).  V = 0 launches nothing."""
-    px = _chk(x_c, torch.float32, 'mesh_lbs: x_c')
-    if x_c.dim() != 2 or x_c.shape[1] != 3:
-        raise RuntimeError(f'mesh_lbs: x_c must be float32 [V,3], got {tuple(x_c.shape)}')
+    px = _mesh_points('mesh_lbs: x_c', x_c)
     V, dev = int(x_c.shape[0]), x_c.device
     pj, pw = _chk(joints, torch.uint8, 'mesh_lbs: joints'), _chk(weights, torch.float32, 'mesh_lbs: weights')
     K = int(joints.shape[1]) if joints.dim() == 2 else -1
@@ -1661,9 +1666,7 @@ def mesh_project(pos, K, E):
     """Vertices through a pinhole camera (occnerf_mesh_project): pos float32 [V,3] on the device, K 3x3 and E 4x4 on the host
     (float64; E is the camera seen from the space of pos) -> (xy int32 [V,2] in 1/256 pixel, z float64 [V], vflag uint8 [V]: 1
     nearer than a millimetre, 2 past the guard band).  V = 0 launches nothing."""
-    pp = _chk(pos, torch.float32, 'mesh_project: pos')
-    if pos.dim() != 2 or pos.shape[1] != 3:
-        raise RuntimeError(f'mesh_project: pos must be float32 [V,3], got {tuple(pos.shape)}')
+    pp = _mesh_points('mesh_project: pos', pos)
     K, E = _host_matrix64(K, (3, 3), 'mesh_project: K'), _host_matrix64(E, (4, 4), 'mesh_project: E')
     if K[0, 1] != 0.0:
         raise NotImplementedError(f'mesh_project: skew K[0,1] = {K[0, 1]!r} is not built')
@@ -1683,13 +1686,16 @@ def mesh_project(pos, K, E):
 
 
 def _mesh_raster_args(who, faces, xy, z, vflag, H, W):
+    """vflag None: an entry that takes none (mesh_resolve_textured); its address comes back as None."""
     pf = _chk(faces, torch.int32, f'{who}: faces')
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise RuntimeError(f'{who}: faces must be int32 [T,3], got {tuple(faces.shape)}')
-    px, pz, pv = _chk(xy, torch.int32, f'{who}: xy'), _chk(z, torch.float64, f'{who}: z'), _chk(vflag, torch.uint8, f'{who}: vflag')
-    V = int(vflag.numel())
-    if tuple(xy.shape) != (V, 2) or tuple(z.shape) != (V,) or not (xy.device == z.device == vflag.device == faces.device):
-        raise RuntimeError(f'{who}: xy [V,2], z [V] and vflag [V] must be mesh_project\'s, on the device of faces')
+    px, pz = _chk(xy, torch.int32, f'{who}: xy'), _chk(z, torch.float64, f'{who}: z')
+    pv = None if vflag is None else _chk(vflag, torch.uint8, f'{who}: vflag')
+    V = int(z.numel())
+    if tuple(xy.shape) != (V, 2) or z.dim() != 1 or not (xy.device == z.device == faces.device) or \
+            (vflag is not None and (tuple(vflag.shape) != (V,) or vflag.device != faces.device)):
+        raise RuntimeError(f"{who}: xy [V,2], z [V]{'' if vflag is None else ' and vflag [V]'} must be mesh_project's, on the device of faces")
     H, W = int(H), int(W)
     if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE and H * W <= MESH_RASTER_MAX_PIXELS):
         raise RuntimeError(f'{who}: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE} or more than 2^28 pixels')
@@ -1738,7 +1744,7 @@ def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
     pc = _chk(colors, torch.uint8, 'mesh_resolve: colors')
     if tuple(colors.shape) != (V, 3) or colors.device != faces.device:
         raise RuntimeError(f'mesh_resolve: colors must be uint8 [{V},3] on the device of faces, got {tuple(colors.shape)}')
-    bg = np.ascontiguousarray(np.clip(np.rint(np.asarray(bgcolor, dtype=np.float64).reshape(3)), 0, 255).astype(np.uint8))
+    bg = _mesh_bgcolor(bgcolor)
     dev = faces.device
     if T == 0 or V == 0:
         return (torch.zeros(H, W, device=dev, dtype=torch.uint8), torch.full((H, W), -1, device=dev, dtype=torch.int32),
@@ -1759,14 +1765,18 @@ def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
 MESH_TEXTURE_MIN_CELL, MESH_TEXTURE_MAX_CELL, MESH_TEXTURE_MAX_SIDE = 4, 64, 16384
 
 
+def _mesh_texture_cell(who, n):
+    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or \
+            not MESH_TEXTURE_MIN_CELL <= int(n) <= MESH_TEXTURE_MAX_CELL:
+        raise RuntimeError(f'{who}: cell = {n!r} is not a whole number in {MESH_TEXTURE_MIN_CELL}..{MESH_TEXTURE_MAX_CELL}')
+    return int(n)
+
+
 def mesh_texture_layout(T, n, who='mesh_texture'):
     """(C, R, W, H, P) of the per-triangle atlas of T >= 1 triangles at cell edge n (4..64): ceil(T / 2) cells of n x n texels,
     C = ceil(sqrt(cells)) per row, R rows, W = C n, H = R n, P = n (n - 1) / 2 texels per triangle.  A cell edge out of range,
     T < 1 and W or H above 16384 are refused by name."""
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or \
-            not MESH_TEXTURE_MIN_CELL <= int(n) <= MESH_TEXTURE_MAX_CELL:
-        raise RuntimeError(f'{who}: cell = {n!r} is not a whole number in {MESH_TEXTURE_MIN_CELL}..{MESH_TEXTURE_MAX_CELL}')
-    T, n = int(T), int(n)
+    T, n = int(T), _mesh_texture_cell(who, n)
     if T < 1:
         raise RuntimeError(f'{who}: T = {T}: a mesh without triangles has no atlas')
     cells = (T + 1) // 2
@@ -1779,22 +1789,13 @@ def mesh_texture_layout(T, n, who='mesh_texture'):
     return C, R, W, H, n * (n - 1) // 2
 
 
-def _mesh_texture_cell(who, n):
-    if isinstance(n, (bool, np.bool_)) or not isinstance(n, (int, np.integer)) or \
-            not MESH_TEXTURE_MIN_CELL <= int(n) <= MESH_TEXTURE_MAX_CELL:
-        raise RuntimeError(f'{who}: cell = {n!r} is not a whole number in {MESH_TEXTURE_MIN_CELL}..{MESH_TEXTURE_MAX_CELL}')
-    return int(n)
-
-
 def mesh_texel_points(verts, faces, n):
     """The canonical points of the atlas' texels (occnerf_mesh_texel_points): verts float32 [V,3], faces int32 [T,3], n the cell
     edge -> pts float32 [T,P,3], P = n (n - 1) / 2, on the device of verts.  A face index outside [0, V) is refused by name
     after one blocking read of the kernel's status word (the kernel itself never uses one as an address).  T = 0 launches
     nothing."""
     n = _mesh_texture_cell('mesh_texel_points', n)
-    pv = _chk(verts, torch.float32, 'mesh_texel_points: verts')
-    if verts.dim() != 2 or verts.shape[1] != 3:
-        raise RuntimeError(f'mesh_texel_points: verts must be float32 [V,3], got {tuple(verts.shape)}')
+    pv = _mesh_points('mesh_texel_points: verts', verts)
     pf = _chk(faces, torch.int32, 'mesh_texel_points: faces')
     if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
         raise RuntimeError(f'mesh_texel_points: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
@@ -1852,19 +1853,12 @@ def mesh_resolve_textured(keys, faces, xy, z, atlas, n, C, bgcolor):
     if keys.dim() != 2:
         raise RuntimeError(f'mesh_resolve_textured: keys must be int64 [H,W], got {tuple(keys.shape)}')
     H, W = (int(s) for s in keys.shape)
-    pf = _chk(faces, torch.int32, 'mesh_resolve_textured: faces')
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise RuntimeError(f'mesh_resolve_textured: faces must be int32 [T,3], got {tuple(faces.shape)}')
-    px, pz = _chk(xy, torch.int32, 'mesh_resolve_textured: xy'), _chk(z, torch.float64, 'mesh_resolve_textured: z')
-    V, T, dev = int(z.numel()), int(faces.shape[0]), faces.device
-    if tuple(xy.shape) != (V, 2) or z.dim() != 1 or not (xy.device == z.device == keys.device == dev):
-        raise RuntimeError('mesh_resolve_textured: xy [V,2] and z [V] must be mesh_project\'s, keys mesh_raster\'s, on the device of faces')
-    if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE and H * W <= MESH_RASTER_MAX_PIXELS):
-        raise RuntimeError(f'mesh_resolve_textured: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE} or more than 2^28 pixels')
-    if T >= 1 << 31 or V >= 1 << 31:
-        raise RuntimeError(f'mesh_resolve_textured: T = {T} / V = {V} reaches the limit of 2^31')
+    pf, px, pz, _, T, V, H, W = _mesh_raster_args('mesh_resolve_textured', faces, xy, z, None, H, W)
+    dev = faces.device
+    if keys.device != dev:
+        raise RuntimeError('mesh_resolve_textured: keys must be mesh_raster\'s, on the device of faces')
     pa, aH, aW, C = _mesh_texture_atlas('mesh_resolve_textured', atlas, T, n, C, dev)
-    bg = np.ascontiguousarray(np.clip(np.rint(np.asarray(bgcolor, dtype=np.float64).reshape(3)), 0, 255).astype(np.uint8))
+    bg = _mesh_bgcolor(bgcolor)
     rgb = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
     with _guard(faces):
         rc = _lib.lib().occnerf_mesh_resolve_textured(pk, pf, T, V, px, pz, H, W, pa, aH, aW, n, C, bg.ctypes.data,

@@ -291,7 +291,7 @@ def run_mesh():
     export_texture) -> mesh/texture.png and texture.json; the image replaces the vertex colours in
     rigged.glb, without the rig it goes into a static mesh/textured.glb, and every mesh_view panel gains a textured render.
     Rank 0 alone works."""
-    from occnerf_amd.mesh import PoseFrames, export_mesh, export_posed
+    from occnerf_amd.mesh import MeshPoser, PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
     cfg.ignore_non_rigid_motions = True
     rank, world, model, loader, _, _ = _setup('tpose')
@@ -340,26 +340,26 @@ def run_mesh():
             if not rigging:
                 size = export_textured(out_dir, kept, normals=bool(m.normals))
                 print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
-        if posing:
-            # the mesh in the pose of frames of the movement source: its body constants only
+        if posing or rigging or viewing:
             cfg.ignore_non_rigid_motions = ignore_non_rigid
+            solver = dict(candidates=int(mp.get('candidates', 3)), max_iter=int(mp.get('max_iter', 20)),
+                          tol=float(mp.get('tol', 1e-7)), non_rigid=bool(mp.get('non_rigid', True)), iter_val=cfg.eval_iter)
+        if posing or rigging:
+            # the movement source's body constants only, and one poser over them: a frame both
+            # mesh_pose.frames and mesh_rig.frames name is solved once
             source = PoseFrames(resolve_dataset_path(cfg, 'movement'), total_frames=int(cfg.render_frames),
                                 bbox_offset=float(cfg.bbox_offset), volume_size=int(cfg.mweight_volume.volume_size))
-            posed = export_posed(model, out_dir, kept, source, mp.frames, candidates=int(mp.candidates), max_iter=int(mp.max_iter),
-                                 tol=float(mp.tol), non_rigid=bool(mp.non_rigid), world=bool(mp.world), normals=bool(m.normals),
-                                 iter_val=cfg.eval_iter)
+            poser = MeshPoser(model, kept['verts'], **solver)
+        if posing:
+            # the mesh in the pose of frames of the movement source
+            posed = export_posed(model, out_dir, kept, source, mp.frames, world=bool(mp.world), normals=bool(m.normals), poser=poser)
             for f in posed['frames']:
                 print(f"posed {f['name']}: {f['not_converged']} not converged, {f['no_bone']} without a bone of {posed['vertices']} "
                       f"vertices, worst residual {f['worst_resid']:.3g} m, {f['mean_iters']:.2f} Newton steps per vertex")
         if rigging:
             # the kept mesh with a skeleton, skin weights and the frames' motion as one glTF
             from occnerf_amd.mesh import export_rig
-            cfg.ignore_non_rigid_motions = ignore_non_rigid
-            source = PoseFrames(resolve_dataset_path(cfg, 'movement'), total_frames=int(cfg.render_frames),
-                                bbox_offset=float(cfg.bbox_offset), volume_size=int(cfg.mweight_volume.volume_size))
-            rigged = export_rig(model, out_dir, kept, source, mrig, candidates=int(mp.get('candidates', 3)),
-                                max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
-                                non_rigid=bool(mp.get('non_rigid', True)), normals=bool(m.normals), iter_val=cfg.eval_iter,
+            rigged = export_rig(model, out_dir, kept, source, mrig, normals=bool(m.normals), poser=poser,
                                 **({'texture': kept['texture']} if texturing else {}))
             print(f"rig: {rigged['vertices']} vertices with up to {rigged['K']} joints each ({rigged['bound_to_root_for_want_of_a_bone']} "
                   f"bound to the root for want of a bone), {len(rigged['frames'])} keys -> {os.path.join(out_dir, 'rigged.glb')} "
@@ -374,13 +374,13 @@ def run_mesh():
             # --type movement opens it, so K, the mask and the photograph are those of the training size
             from occnerf_amd.dataset import PreparedDataset
             from occnerf_amd.mesh_view import export_views
-            cfg.ignore_non_rigid_motions = ignore_non_rigid
             dev = torch.device('cuda', torch.cuda.current_device())
             dataset = PreparedDataset.from_cfg(cfg, resolve_dataset_path(cfg, 'movement'), device=None, prepare_device=dev)
-            views = export_views(model, out_dir, kept, dataset, mv.frames, candidates=int(mp.get('candidates', 3)),
-                                 max_iter=int(mp.get('max_iter', 20)), tol=float(mp.get('tol', 1e-7)),
-                                 non_rigid=bool(mp.get('non_rigid', True)), panels=bool(mv.get('panels', True)),
-                                 bgcolor=cfg.bgcolor, iter_val=cfg.eval_iter,
+            # (a poser of its own, which keeps nothing: the dataset's frames are not the indices of the source above; that
+            # one's kept frames go first)
+            poser = MeshPoser(model, kept['verts'], keep=False, **solver)
+            views = export_views(model, out_dir, kept, dataset, mv.frames, panels=bool(mv.get('panels', True)), bgcolor=cfg.bgcolor,
+                                 poser=poser,
                                  **({'texture': kept['texture']} if texturing else {}))
             for f in views['frames']:
                 iou = 'none (empty union)' if f['iou'] is None else f"{f['iou']:.4f}"

@@ -219,3 +219,38 @@ def test_wrappers_refuse_host_tensors_and_the_sources_agree():
     src = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_pose.hip')).read()
     assert 'fma' not in re.sub(r'//[^\n]*', '', src).lower() and 'atomic' not in re.sub(r'//[^\n]*', '', src).lower()
     assert 'kPoseClamp = 1e-4' in src and mp.CLAMP == 1e-4
+
+
+@pytest.mark.parametrize('key', ['mesh_pose.frames', 'mesh_view.frames'])
+def test_frame_indices_are_one_rule_under_every_key(key):
+    """mesh._frame_indices serves export_posed, export_rig and mesh_view.export_views: the same list and the same refusal,
+    named after the key that asked."""
+    from occnerf_amd import mesh
+    source = mesh.PoseFrames(None, total_frames=7)
+    assert mesh._frame_indices(source, 'all', key) == list(range(7))
+    assert mesh._frame_indices(source, [6, 0, 3, 3], key) == [6, 0, 3, 3]
+    assert mesh._frame_indices(source, (np.int64(2), 5.0), key) == [2, 5] and mesh._frame_indices(source, [], key) == []
+    for bad in ([0, 7], [-1], [3, 100]):
+        with pytest.raises(RuntimeError, match=f'^{re.escape(key)}: frame {bad[-1]} outside the 7 frames of the source$'):
+            mesh._frame_indices(source, bad, key)
+
+
+def test_export_views_refuses_a_frame_through_the_shared_rule():
+    """mesh_view.export_views takes its frame list from mesh._frame_indices: the refusal is that function's, before anything is
+    posed or written (a network that is only a device and a source that is only a length get that far)."""
+    import types
+
+    import torch
+    from occnerf_amd import mesh_view
+    net = types.SimpleNamespace(point_base=torch.zeros(1))
+    with pytest.raises(RuntimeError, match='^mesh_view.frames: frame 7 outside the 7 frames of the source$'):
+        mesh_view.export_views(net, os.devnull, {}, range(7), [0, 7])
+
+
+def test_shared_mesh_header_keeps_the_kernels_rules():
+    """What mesh_raster.hip and mesh_texture.hip share lives in mesh_screen.h: it holds no fused multiply-add and no atomic of
+    its own, and every object file is rebuilt when it changes."""
+    make = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'Makefile')).read()
+    rule = re.search(r'^build/%\.o:.*$', make, flags=re.M).group(0)
+    src = re.sub(r'//[^\n]*', '', open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_screen.h')).read()).lower()
+    assert 'fma' not in src and 'atomic' not in src and re.search(r'\bmesh_screen\.h\b', rule)

@@ -366,3 +366,42 @@ def test_export_rig_without_correctives(ops, seeded, tmp_path):
     with pytest.raises(RuntimeError, match='mesh_rig.influences = 6'):
         mesh.export_rig(net, str(tmp_path / 'no'), kept, source, {**rig8, 'influences': 6})
     assert not (tmp_path / 'no').exists()
+
+
+def test_one_poser_serves_both_exports(seeded, tmp_path):
+    """export_posed then export_rig (K = 8, no correctives) on the 48 body points through one shared mesh.MeshPoser, against the
+    same two calls with a poser of their own: the files byte for byte, the sidecars outside their wall times, and every one of
+    the three frames solved once, not once per export."""
+    from occnerf_amd import mesh
+    s, net = seeded, seeded['net']
+    verts = np.ascontiguousarray(s['pts'][np.arange(0, 6890, 144)[:48]])
+    kept = {'verts': T(verts), 'faces': np.arange(48, dtype=np.int32).reshape(16, 3),
+            'colors': (np.arange(48 * 3) % 251).astype(np.uint8).reshape(48, 3)}
+    source, frames = mesh.PoseFrames(None, total_frames=100), list(mp.FRAMES)
+    rig8 = {**mesh.RIG_DEFAULTS, 'enable': True, 'frames': frames, 'influences': 8}
+    poser = mesh.MeshPoser(net, kept['verts'])
+    assert poser.solved == 0
+    infos = {}
+    for name, shared in (('shared', poser), ('own', None)):
+        out = str(tmp_path / name)
+        infos[name] = (mesh.export_posed(net, out, kept, source, frames, poser=shared),
+                       mesh.export_rig(net, out, kept, source, rig8, poser=shared))
+        if shared is not None:
+            assert poser.solved == 3                      # after export_posed and export_rig: 3, not 6
+    assert poser.solved == len(frames) == 3
+    files = ['rigged.glb'] + [f'posed/frame_{i:06d}.ply' for i in frames]
+    assert sorted(os.listdir(tmp_path / 'shared' / 'posed')) == sorted(os.path.basename(f) for f in files[1:])
+    for f in files:
+        assert (tmp_path / 'shared' / f).read_bytes() == (tmp_path / 'own' / f).read_bytes(), f
+
+    def timeless(d):
+        if isinstance(d, dict):
+            return {k: timeless(v) for k, v in d.items() if k != 'seconds'}
+        return [timeless(v) for v in d] if isinstance(d, list) else d
+    for k, name in enumerate(('posed.json', 'rig.json')):
+        a, b = (json.loads((tmp_path / w / name).read_text()) for w in ('shared', 'own'))
+        assert timeless(a) == timeless(b) and list(a) == list(b) and len(a['frames']) == 3
+        assert timeless(infos['shared'][k]) == timeless(infos['own'][k])
+    posed, rigged = (json.loads((tmp_path / 'shared' / name).read_text()) for name in ('posed.json', 'rig.json'))
+    assert all(set(f['seconds']) == {'unoffset', 'pose', 'write'} for f in posed['frames'])
+    assert set(rigged['seconds']) == {'keys', 'skin', 'pose', 'lbs', 'report', 'write'}

@@ -20,6 +20,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             values read, from which the kernel's achieved bytes per second follow;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import importlib.util
 import json
 import os
@@ -95,7 +96,9 @@ def cmd_device(a):
             res[f'{name}_frame{idx}'] = {
                 'vertices': V, 'converged_share': round(counts[0] / V, 4), 'not_converged_share': round(counts[1] / V, 4),
                 'no_bone_share': round(counts[2] / V, 4), 'mean_iters': round(float(out[2].float().mean().item()), 3),
-                'worst_resid_converged': float(out[3][flag == 0].max().item()) if counts[0] else None}
+                'worst_resid_converged': float(out[3][flag == 0].max().item()) if counts[0] else None,
+                # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                'sha256': {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest() for k, t in zip(('p', 'flag', 'iters', 'resid'), out)}}
             for k, t in zip(('p', 'flag', 'iters', 'resid'), out):
                 saved[f'{name}{idx}_{k}'] = t[sub].cpu().numpy()
         res[f'mesh_frame{idx}']['non_rigid_fixed_point_wall_ms'] = round(fixed_ms, 2)

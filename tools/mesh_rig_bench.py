@@ -18,6 +18,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             and its results against the device's;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import importlib.util
 import json
 import os
@@ -93,6 +94,9 @@ def cmd_device(a):
             n = count.cpu().numpy()
             share = kept.cpu().numpy().astype(np.float64)[n > 0]
             entry = {'vertices': V, 'influences_histogram': np.bincount(n, minlength=K + 1).tolist(),
+                     # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                     'sha256': {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                                for k, t in zip(('joints', 'weights', 'count', 'kept'), out)},
                      'kept_share': {'min': float(share.min()), 'mean': float(share.mean()), 'p01': float(np.percentile(share, 1))}}
             for F in (1, 16):
                 R, T_, tg, tf = Rs[:F].contiguous(), Ts[:F].contiguous(), target[:F].contiguous(), tflag[:F].contiguous()

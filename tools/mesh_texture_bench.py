@@ -17,6 +17,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             time, and its results against the device's;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import importlib.util
 import json
 import os
@@ -107,7 +108,10 @@ def cmd_device(a):
                      'atlas': [W, H], 'texels_queried': T * P, 'unowned_share': 1.0 - float(T * P) / float(W * H),
                      'bytes': {'points': T * P * 12, 'colours': T * P * 12, 'atlas': W * H * 3},
                      'view': [VIEW, VIEW], 'view_pixels_covered': int(cover.sum().item()),
-                     'colour_query_wall_ms': _stats(query)}
+                     'colour_query_wall_ms': _stats(query),
+                     # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                     'sha256': {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                                for k, t in (('atlas', atlas), ('resolve_textured', image), ('resolve_vertex_colours', plain))}}
         # the first SUBSET triangles on their own, for the numpy definition
         S = min(SUBSET, T)
         fs = faces[:S].contiguous()

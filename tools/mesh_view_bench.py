@@ -19,6 +19,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             its outputs against the device's, byte for byte;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import importlib.util
 import json
 import os
@@ -98,7 +99,9 @@ def cmd_device(a):
         keys, counts = ops.mesh_raster(f, xy, z, vflag, H, W, faces_checked=True)
         n = dict(zip(mesh_view.COUNTS, one['counts'].tolist()))
         res[name] = {'vertices': int(p.shape[0]), 'triangles': int(f.shape[0]), 'counts': n,
-                     'flagged_vertices': int((one['vflag'] != 0).sum().item())}
+                     'flagged_vertices': int((one['vflag'] != 0).sum().item()),
+                     # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                     'sha256': {k: hashlib.sha256(one[k].cpu().numpy().tobytes()).hexdigest() for k in OUTPUTS}}
         runs[name, 'project'] = lambda p=p: ops.mesh_project(p, K, E)
         runs[name, 'raster'] = lambda f=f, xy=xy, z=z, vflag=vflag: ops.mesh_raster(f, xy, z, vflag, H, W, faces_checked=True)
         runs[name, 'resolve'] = lambda f=f, xy=xy, z=z, vflag=vflag, c=c, keys=keys, counts=counts: \
