@@ -944,6 +944,39 @@ int occnerf_mesh_resolve_textured(const uint64_t *keys, const int32_t *faces, in
                                   const double *z, int32_t Himg, int32_t Wimg, const uint8_t *atlas, int32_t aH, int32_t aW,
                                   int32_t n, int32_t C, const uint8_t *h_bgcolor, uint8_t *rgb, void *stream);
 
+/* The photographs of a prepared dataset on the atlas (occnerf_amd/mesh.py project_photos / export_photo_texture, run.py --type
+ * mesh mesh_photo.enable).  The reference has no counterpart of these two entries.  Bit-identical to
+ * tests/mesh_photo_restatement.py; integers on the colour path, no atomics (a texel belongs to one thread), the same bytes on
+ * every run. */
+
+/* No counterpart in the reference.  One frame onto the accumulators acc[T P,4] int64 (sum of w s per channel, sum of w) and
+ * seen[T P] int32, IN/OUT, zeroed by the caller before the first frame.  xy[T P,2] / z[T P] / vflag[T P]: occnerf_mesh_project
+ * of occnerf_mesh_texel_points(verts, faces, n); verts[V,3] float32 the posed vertices, pflag[V] uint8 their posing flags;
+ * keys[H*W]: occnerf_mesh_raster of the same verts and faces; photo[H*W,3] uint8, inside[H*W] uint8; the HOST h_K[9], h_E[16]
+ * as occnerf_mesh_project takes them.  First launch, one thread per triangle -> tri_w[T] int32: with c_k the camera-space
+ * vertices, e1 = c1 - c0, e2 = c2 - c0, N = e1 x e2, g = (c0 + c1) + c2, d = N.g, w = min(rint(256 ((d d) / ((N.N)(g.g)))), 256)
+ * in fp64, one rounding per operator; 0 when (N.N)(g.g) is 0 or not finite or a vertex carries a posing flag or a flag of
+ * occnerf_mesh_project; -1 when d > 0 (the triangle faces away); a face with an index outside [0, V) gets 0 and sets
+ * status[0] (int32, zeroed by the caller) to 1, and no such index is used as an address.  Second launch, one thread per texel:
+ * seen in this frame when tri_w > 0, vflag == 0, the taps (Y >> 8 + {0,1}, X >> 8 + {0,1}) all lie inside the image, have
+ * inside != 0, a key that is not all ones and z <= double(float32 depth of the key) + bias; then with fx = X & 255,
+ * fy = Y & 255, s_c = (256-fx)(256-fy) c00 + fx (256-fy) c01 + (256-fx) fy c10 + fx fy c11 (c01 the next column, c10 the next
+ * row): acc_c += w s_c, acc_3 += w, seen += 1.  No tap address is formed before the inside-image test.  Refused: a null
+ * pointer, n outside 4..64, H or W outside 1..16384, T P >= 2^31, a skew K[0,1] != 0, bias negative or NaN.  T = 0 returns 0
+ * without a launch. */
+int occnerf_mesh_texture_project(const int32_t *xy, const double *z, const uint8_t *vflag, const float *verts,
+                                 const uint8_t *pflag, int64_t V, const int32_t *faces, int64_t T, int32_t n, const double *h_K,
+                                 const double *h_E, const uint64_t *keys, const uint8_t *photo, const uint8_t *inside, int32_t H,
+                                 int32_t W, double bias, int64_t *acc, int32_t *seen, int32_t *tri_w, int32_t *status,
+                                 void *stream);
+/* No counterpart in the reference.  One thread per owned texel: seen_img[H,W] uint8 (IN/OUT, zeroed by the caller) receives
+ * min(seen, 255) at the texel's place (occnerf_mesh_texture_fill's); atlas[H,W,3] uint8, IN/OUT, the caller's copy of the
+ * field's atlas, receives min((acc_c + 32768 acc_3) / (65536 acc_3), 255) in int64 where seen >= min_seen (>= 1) and
+ * acc_3 > 0; every other byte stays.  The layout is refused as occnerf_mesh_texture_fill refuses it.  T = 0 returns 0
+ * without a launch. */
+int occnerf_mesh_texture_blend(const int64_t *acc, const int32_t *seen, int64_t T, int32_t n, int32_t C, int32_t H, int32_t W,
+                               int32_t min_seen, uint8_t *atlas, uint8_t *seen_img, void *stream);
+
 /* Collapsed samples, classified once in front of the kNN and feature kernels (no counterpart in the
  * reference).  One lane per entry o of the live list rows[0 .. *n_dev) (capacity N_max): flag[o] = 1 iff xyz[rows[o]] lies
  * inside the radius of center[4] (the |p - c|^2 < r^2 test of the kNN and feature kernels) AND the encoder input x[4] the

@@ -155,6 +155,13 @@ _DEFAULTS = {
     # mesh/textured.glb, in place of the vertex colours; cell: the edge in texels (4..64) of the atlas cell two triangles share
     # -- a triangle's edge spans cell - 3 texels --; fill: the colour 0..255 of the texels no triangle owns
     'mesh_texture': {'enable': False, 'cell': 8, 'fill': [0, 0, 0]},
+    # run.py --type mesh, the photographs of the prepared dataset on the atlas (occnerf_amd/mesh.py export_photo_texture, DESIGN.md
+    # section 7p; needs mesh_texture.enable and a prepared dataset): enable writes mesh/texture_photo.png (what the frames saw,
+    # the colour field elsewhere), texture_seen.png (how many frames saw each texel) and texture_photo.json; frames: 'all' or a
+    # list of frame indices; bias: the depth tolerance in metres of the visibility test (None: the mesh's voxel edge); min_seen:
+    # the frames that must have seen a texel before their mean replaces the field's colour; in_glb: the photo atlas goes into
+    # rigged.glb / textured.glb in place of texture.png
+    'mesh_photo': {'enable': False, 'frames': 'all', 'bias': None, 'min_seen': 1, 'in_glb': True},
     # run.py --type mesh, the posed mesh seen from its frame's camera (occnerf_amd/mesh_view.py export_views, DESIGN.md section
     # 7j): frames = None (nothing happens), a list of frame indices of the movement source's prepared dataset, or 'all'; per
     # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the

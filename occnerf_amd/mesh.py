@@ -24,12 +24,20 @@ counterpart there.
   atlas_layout, texture_uv, bake_texture, export_texture
                  the mesh's colour as a texture (mesh_texture.enable): a per-triangle atlas whose texels
                  are canonical points (csrc/mesh_texture.hip), coloured by Network.query_canonical -> texture.png, texture.json
-                 and the image inside rigged.glb or a static textured.glb.
+                 and the image inside rigged.glb or a static textured.glb;
+  check_photo, project_photos, export_photo_texture
+                 the photographs of a prepared dataset on that atlas (mesh_photo.enable): per frame the
+                 posed mesh's texels through the frame's camera, tested against the rasteriser's depth keys and the frame's
+                 mask and summed in integers (csrc/mesh_texture.hip mesh_texture_project / mesh_texture_blend) ->
+                 texture_photo.png (the frames' weighted mean where a frame saw the texel, the colour field elsewhere),
+                 texture_seen.png (how many frames saw each texel) and texture_photo.json.
 
 Every step is a pure function of its inputs: the same checkpoint and settings give the same PLY byte for byte (the sidecars
 differ in their wall times only).  Decimation, smoothing, hole filling, OBJ, a mesh welded from the f16x3 kernels' field,
 area-proportional or merged texture charts, mip-safe padding and normal maps are not offered; nor, for the posed mesh, roots of
-the warp other than the owning bone's or changes of topology."""
+the warp other than the owning bone's or changes of topology; nor, for the photo texture, a robust blend (median, best frame),
+exposure compensation between frames, the all_cameras.pkl rig, a pose refined against the photograph or anything that repairs a
+wrong mask."""
 import json
 import math
 import os
@@ -249,7 +257,8 @@ def write_ply(path, verts, faces, colors, normals=None):
 def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, normals=True, chunk=1 << 21, keep=None,
                 components='all', drop_cavities=False):
     """<out_dir>/mesh.ply and mesh.json of the canonical body -> the sidecar's dict.  keep: a dict that receives what
-    export_posed needs of the mesh ('verts' float32 [V,3] on the device, 'faces' int32 [T,3] and 'colors' uint8 [V,3] numpy).
+    export_posed needs of the mesh ('verts' float32 [V,3] on the device, 'faces' int32 [T,3] and 'colors' uint8 [V,3] numpy, 'h'
+    the voxel edge).
     components / drop_cavities: the clean-up of DESIGN.md section 7m; at their defaults nothing is labelled and the files are
     those written without them.  Otherwise the colours, the normals and `keep` are those of the kept mesh, and the sidecar
     gains 'components', 'extracted_vertices' / 'extracted_triangles' and seconds['components']."""
@@ -279,7 +288,7 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
                       f'{float(np.float32(used)):g}): the mesh is open there and is written as it is')
     v, f = verts.cpu().numpy(), faces.cpu().numpy()
     if keep is not None:
-        keep.update(verts=verts, faces=f, colors=colors)
+        keep.update(verts=verts, faces=f, colors=colors, h=h)
     os.makedirs(out_dir, exist_ok=True)
     write_ply(os.path.join(out_dir, 'mesh.ply'), v, f, colors, _normals(v, f, normals))
     info = {'resolution': int(resolution), 'h': h, 'level': float(np.float32(used)), 'level_is_default': level is None,
@@ -740,3 +749,142 @@ def export_textured(out_dir, kept, normals=True):
     v, faces, tex = kept['verts'].cpu().numpy(), kept['faces'], kept['texture']
     return gltf.write_glb(os.path.join(out_dir, 'textured.glb'), v, faces, None, None, None, None,
                           normals=_normals(v, faces, normals), texture={'uv': tex['uv'], 'png': tex['png']})
+
+
+# ------------------------------------------------------------------ the photographs on the atlas
+PHOTO_DEFAULTS = {'enable': False, 'frames': 'all', 'bias': None, 'min_seen': 1, 'in_glb': True}
+SEEN_BUCKETS = (('0', 0, 0), ('1', 1, 1), ('2-3', 2, 3), ('4-7', 4, 7), ('8-15', 8, 15), ('16+', 16, (1 << 31) - 1))
+
+
+def check_photo(photo):
+    """The mesh_photo keys as export_photo_texture takes them (a dict with every key of PHOTO_DEFAULTS); a value out of range is
+    refused by name."""
+    photo = {k: (photo.get(k, v) if hasattr(photo, 'get') else v) for k, v in PHOTO_DEFAULTS.items()}
+    for key in ('enable', 'in_glb'):
+        if not isinstance(photo[key], (bool, np.bool_)):
+            raise RuntimeError(f'mesh_photo.{key} = {photo[key]!r}: True or False')
+
+    def whole(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    frames = photo['frames']
+    if not (isinstance(frames, str) and frames == 'all') and not (
+            hasattr(frames, '__len__') and not isinstance(frames, str) and len(frames) > 0 and all(whole(i) and int(i) >= 0 for i in frames)):
+        raise RuntimeError(f"mesh_photo.frames = {frames!r}: 'all' or a list of frame indices of the prepared dataset, at least one")
+    photo['frames'] = frames if isinstance(frames, str) else [int(i) for i in frames]
+    bias = photo['bias']
+    if bias is not None:
+        if isinstance(bias, (bool, np.bool_)) or not isinstance(bias, (int, float, np.integer, np.floating)) or \
+                not 0.0 <= float(bias) < float('inf'):
+            raise RuntimeError(f'mesh_photo.bias = {bias!r}: None (the voxel edge of the mesh) or a finite number of metres >= 0')
+        photo['bias'] = float(bias)
+    if not whole(photo['min_seen']) or not 1 <= int(photo['min_seen']) < 1 << 31:
+        raise RuntimeError(f"mesh_photo.min_seen = {photo['min_seen']!r}: a whole number of frames >= 1")
+    photo['min_seen'] = int(photo['min_seen'])
+    return photo
+
+
+def project_photos(frames_iter, faces, n, bias):
+    """(acc int64 [T P,4], seen int32 [T P], per-frame figures): the frames summed onto the atlas of cell edge n of the mesh
+    `faces` int32 [T,3] (on the GPU).  frames_iter yields (p float32 [V,3], flag uint8 [V], K, E, photo uint8 [H,W,3], inside
+    uint8 [H,W]) with the tensors on the device of faces: the posed vertices and their posing flags, the frame's intrinsics and
+    body-space extrinsics (host), the photograph and the mask's inside.  Per frame: ops.mesh_texel_points of the posed vertices,
+    ops.mesh_project of the texels and of the vertices, ops.mesh_raster, ops.mesh_texture_project.  Where the posed vertices
+    come from is the caller's business."""
+    n, T = int(n), int(faces.shape[0])
+    dev, P = faces.device, int(n) * (int(n) - 1) // 2
+    acc = torch.zeros(T * P, 4, device=dev, dtype=torch.int64)
+    seen = torch.zeros(T * P, device=dev, dtype=torch.int32)
+    figures, total = [], 0
+    for p, flag, K, E, photo, inside in frames_iter:
+        H, W = int(photo.shape[0]), int(photo.shape[1])
+        p = p.detach().contiguous()
+        t0 = _clock(dev)
+        q = ops.mesh_texel_points(p, faces, n).reshape(-1, 3)                 # (refuses a face index outside [0, V) by name)
+        t1 = _clock(dev)
+        xy, z, vflag = ops.mesh_project(q, K, E)
+        vxy, vz, vvflag = ops.mesh_project(p, K, E)
+        t2 = _clock(dev)
+        keys, _ = ops.mesh_raster(faces, vxy, vz, vvflag, H, W, faces_checked=True)
+        t3 = _clock(dev)
+        tri_w = ops.mesh_texture_project(xy, z, vflag, p, flag, faces, n, K, E, keys, photo, inside, bias, acc, seen)
+        t4 = _clock(dev)
+        now, away, used = (int(v) for v in torch.stack([seen.sum(), (tri_w < 0).sum(), (tri_w > 0).sum()]).tolist())
+        figures.append({'texels_seen': now - total, 'triangles_facing_away': away, 'triangles_weighted': used,
+                        'seconds': {'points': round(t1 - t0, 4), 'project': round(t2 - t1, 4), 'raster': round(t3 - t2, 4),
+                                    'accumulate': round(t4 - t3, 4)}})
+        total = now
+    return acc, seen, figures
+
+
+def seen_histogram(seen):
+    """The seen counts of the owned texels in the buckets 0, 1, 2-3, 4-7, 8-15, 16+ -> a dict of whole numbers."""
+    counts = torch.stack([((seen >= lo) & (seen <= hi)).sum() for _, lo, hi in SEEN_BUCKETS]).tolist()
+    return {name: int(c) for (name, _, _), c in zip(SEEN_BUCKETS, counts)}
+
+
+def export_photo_texture(net, out_dir, kept, dataset, photo=None, poser=None, candidates=3, max_iter=20, tol=1e-7, non_rigid=True,
+                         iter_val=1e7):
+    """<out_dir>/texture_photo.png, texture_seen.png and texture_photo.json of the kept mesh, whose field texture export_texture
+    has baked (kept['texture']) -> the sidecar's dict.  dataset: a dataset.PreparedDataset; the frames mesh_photo.frames of it are
+    posed as export_posed and mesh_view.export_views pose them (poser: a MeshPoser of kept['verts'] over the dataset; None: one
+    is built here from candidates .. iter_val), photographed by truth_u8 and masked by gt_alpha > 0.5.  kept receives
+    'texture_photo': {'atlas', 'seen' (device tensors), 'n', 'C', 'uv', 'png', 'frames'}."""
+    import io
+
+    from PIL import Image
+    photo = check_photo(PHOTO_DEFAULTS if photo is None else photo)
+    if dataset is None:
+        raise RuntimeError('mesh_photo.enable: the photographs and masks are those of a prepared dataset; the synthetic frame '
+                           'source has none (set train.dataset_path or movement.dataset)')
+    if 'texture' not in kept:
+        raise RuntimeError('mesh_photo.enable: the photographs are blended into the atlas of mesh_texture.enable, which is not set')
+    dev = net.point_base.device
+    tex, verts = kept['texture'], kept['verts']
+    n, C = int(tex['n']), int(tex['C'])
+    idxs = _frame_indices(dataset, photo['frames'], 'mesh_photo.frames')
+    bias = float(kept['h']) if photo['bias'] is None else float(photo['bias'])
+    poser = MeshPoser.of(poser, net, verts, candidates, max_iter, tol, non_rigid, iter_val, keep=False)
+    f_host = np.ascontiguousarray(np.asarray(kept['faces'], dtype=np.int32).reshape(-1, 3))
+    faces = torch.from_numpy(f_host).to(dev)
+    T, P = int(f_host.shape[0]), n * (n - 1) // 2
+    pose_seconds = []
+
+    def frames_iter():
+        for i in idxs:
+            f = dataset.frames[i]
+            t0 = _clock(dev)
+            _, _, p, flag, _, _, _ = poser.frame(i, _device_frame(dataset.host_constants(i), dev))
+            pose_seconds.append(_clock(dev) - t0)
+            truth = torch.from_numpy(np.ascontiguousarray(dataset.truth_u8(i))).to(dev)
+            inside = torch.from_numpy(np.ascontiguousarray((np.asarray(dataset.gt_alpha(i)) > 0.5).astype(np.uint8))).to(dev)
+            yield p, flag, f['K'], f['E'], truth, inside
+    t0 = _clock(dev)
+    acc, seen, figures = project_photos(frames_iter(), faces, n, bias)
+    t1 = _clock(dev)
+    atlas, seen_img = ops.mesh_texture_blend(acc, seen, T, n, C, tex['atlas'], photo['min_seen'])
+    t2 = _clock(dev)
+    hist = seen_histogram(seen)
+    os.makedirs(out_dir, exist_ok=True)
+    blobs = {}
+    for name, img in (('texture_photo.png', atlas), ('texture_seen.png', seen_img)):
+        blob = io.BytesIO()
+        Image.fromarray(img.cpu().numpy()).save(blob, format='PNG')
+        blobs[name] = blob.getvalue()
+        with open(os.path.join(out_dir, name), 'wb') as out:
+            out.write(blobs[name])
+    t3 = time.perf_counter()
+    for i, row, sec in zip(idxs, figures, pose_seconds):
+        row.update(frame=i, name=dataset.frames[i]['frame_name'])
+        row['seconds']['pose_and_load'] = round(sec, 4)
+    owned = T * P
+    info = {'frames': idxs, 'bias_m': bias, 'bias_is_voxel_edge': photo['bias'] is None, 'min_seen': photo['min_seen'],
+            'n': n, 'C': C, 'H': int(atlas.shape[0]), 'W': int(atlas.shape[1]), 'triangles': T, 'owned_texels': owned,
+            'seen_share': (owned - hist['0']) / owned if owned else None, 'seen_histogram': hist,
+            'texels_blended': int((seen >= photo['min_seen']).sum().item()), 'per_frame': figures,
+            'bytes': {'accumulators': owned * (4 * 8 + 4), 'png': len(blobs['texture_photo.png']), 'seen_png': len(blobs['texture_seen.png'])},
+            'seconds': {'frames': round(t1 - t0, 4), 'pose_and_load': round(sum(pose_seconds), 4), 'blend': round(t2 - t1, 4),
+                        'write': round(t3 - t2, 4)}}
+    kept['texture_photo'] = {'atlas': atlas, 'seen': seen_img, 'n': n, 'C': C, 'uv': tex['uv'], 'png': blobs['texture_photo.png'],
+                             'frames': list(idxs)}
+    _write_sidecar(os.path.join(out_dir, 'texture_photo.json'), info)
+    return info

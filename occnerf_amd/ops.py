@@ -1867,6 +1867,91 @@ def mesh_resolve_textured(keys, faces, xy, z, atlas, n, C, bgcolor):
     return rgb
 
 
+# ------------------------------------------------------------------ the photographs on the atlas
+def mesh_texture_project(xy, z, vflag, verts, pflag, faces, n, K, E, keys, photo, inside, bias, acc, seen):
+    """One frame onto the atlas' accumulators (occnerf_mesh_texture_project): xy int32 [T P,2] / z float64 [T P] / vflag uint8
+    [T P] are mesh_project's of mesh_texel_points(verts, faces, n); verts float32 [V,3] the posed vertices, pflag uint8 [V]
+    their posing flags, faces int32 [T,3]; K 3x3 and E 4x4 on the host as mesh_project takes them; keys int64 [H,W]
+    mesh_raster's of the same verts and faces; photo uint8 [H,W,3], inside uint8 [H,W]; bias >= 0 in metres; acc int64 [T P,4]
+    and seen int32 [T P] are written IN PLACE -> tri_w int32 [T]: the triangles' weights in this frame, 1..256, 0 unusable,
+    -1 facing away.  A face index outside [0, V) is refused by name after one blocking read of the status word (no such index
+    is used as an address).  T = 0 launches nothing."""
+    who = 'mesh_texture_project'
+    n = _mesh_texture_cell(who, n)
+    pv = _mesh_points(f'{who}: verts', verts)
+    pp = _chk(pflag, torch.uint8, f'{who}: pflag')
+    pf = _chk(faces, torch.int32, f'{who}: faces')
+    dev = verts.device
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != dev:
+        raise RuntimeError(f'{who}: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
+    V, T, P = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2
+    if V >= 1 << 31 or T * P >= 1 << 31:
+        raise RuntimeError(f'{who}: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
+    N = T * P
+    px, pz, pw = _chk(xy, torch.int32, f'{who}: xy'), _chk(z, torch.float64, f'{who}: z'), _chk(vflag, torch.uint8, f'{who}: vflag')
+    pk, ph, pi = _chk(keys, torch.int64, f'{who}: keys'), _chk(photo, torch.uint8, f'{who}: photo'), _chk(inside, torch.uint8, f'{who}: inside')
+    pa, ps = _chk(acc, torch.int64, f'{who}: acc'), _chk(seen, torch.int32, f'{who}: seen')
+    if tuple(pflag.shape) != (V,) or tuple(xy.shape) != (N, 2) or tuple(z.shape) != (N,) or tuple(vflag.shape) != (N,):
+        raise RuntimeError(f'{who}: pflag must be [{V}] and xy / z / vflag [{N},2] / [{N}] / [{N}], got {tuple(pflag.shape)}, '
+                           f'{tuple(xy.shape)}, {tuple(z.shape)}, {tuple(vflag.shape)}')
+    if keys.dim() != 2:
+        raise RuntimeError(f'{who}: keys must be int64 [H,W], got {tuple(keys.shape)}')
+    H, W = (int(s) for s in keys.shape)
+    if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE):
+        raise RuntimeError(f'{who}: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE}')
+    if tuple(photo.shape) != (H, W, 3) or tuple(inside.shape) != (H, W):
+        raise RuntimeError(f'{who}: photo must be uint8 [{H},{W},3] and inside uint8 [{H},{W}], got {tuple(photo.shape)} and '
+                           f'{tuple(inside.shape)}')
+    if tuple(acc.shape) != (N, 4) or tuple(seen.shape) != (N,):
+        raise RuntimeError(f'{who}: acc must be int64 [{N},4] and seen int32 [{N}], got {tuple(acc.shape)} and {tuple(seen.shape)}')
+    if not all(t.device == dev for t in (pflag, xy, z, vflag, keys, photo, inside, acc, seen)):
+        raise RuntimeError(f'{who}: every tensor must be on the device of verts')
+    K, E = _host_matrix64(K, (3, 3), f'{who}: K'), _host_matrix64(E, (4, 4), f'{who}: E')
+    if K[0, 1] != 0.0:
+        raise NotImplementedError(f'{who}: skew K[0,1] = {K[0, 1]!r} is not built')
+    bias = float(bias)
+    if not bias >= 0.0:
+        raise RuntimeError(f'{who}: bias = {bias!r} is negative or not a number')
+    tri_w = torch.zeros(T, device=dev, dtype=torch.int32)
+    if T == 0:
+        return tri_w
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _guard(verts):
+        rc = _lib.lib().occnerf_mesh_texture_project(px, pz, pw, pv, pp, V, pf, T, n, K.ctypes.data_as(C.c_void_p),
+                                                     E.ctypes.data_as(C.c_void_p), pk, ph, pi, H, W, bias, pa, ps,
+                                                     tri_w.data_ptr(), status.data_ptr(), _stream(verts))
+    _lib.check(rc, who)
+    if int(status.item()) != 0:
+        raise RuntimeError(f'{who}: a face index lies outside [0, {V})')
+    return tri_w
+
+
+def mesh_texture_blend(acc, seen, T, n, C, atlas, min_seen=1):
+    """The accumulators as an atlas (occnerf_mesh_texture_blend): acc int64 [T P,4], seen int32 [T P], atlas uint8 [H,W,3] the
+    field's (mesh_texture_fill's; not written) -> (photo uint8 [H,W,3], seen_img uint8 [H,W]): an owned texel with
+    seen >= min_seen carries (acc_c + 32768 acc_3) // (65536 acc_3), every other texel atlas' byte; seen_img holds
+    min(seen, 255) at the owned texels and 0 elsewhere.  T = 0 launches nothing."""
+    who = 'mesh_texture_blend'
+    n = _mesh_texture_cell(who, n)
+    pa, ps = _chk(acc, torch.int64, f'{who}: acc'), _chk(seen, torch.int32, f'{who}: seen')
+    T, P = int(T), n * (n - 1) // 2
+    if T < 0 or T * P >= 1 << 31 or tuple(acc.shape) != (T * P, 4) or tuple(seen.shape) != (T * P,) or seen.device != acc.device:
+        raise RuntimeError(f'{who}: acc must be int64 [{T} x {P},4] and seen int32 [{T} x {P}] with T P < 2^31 on one device, got '
+                           f'{tuple(acc.shape)} and {tuple(seen.shape)}')
+    if isinstance(min_seen, (bool, np.bool_)) or not isinstance(min_seen, (int, np.integer)) or not 1 <= int(min_seen) < 1 << 31:
+        raise RuntimeError(f'{who}: min_seen = {min_seen!r} is not a whole number >= 1')
+    _, H, W, C = _mesh_texture_atlas(who, atlas, T, n, C, acc.device)
+    out = atlas.clone()
+    seen_img = torch.zeros(H, W, device=acc.device, dtype=torch.uint8)
+    if T == 0:
+        return out, seen_img
+    with _guard(acc):
+        rc = _lib.lib().occnerf_mesh_texture_blend(pa, ps, T, n, C, H, W, int(min_seen), out.data_ptr(), seen_img.data_ptr(),
+                                                   _stream(acc))
+    _lib.check(rc, who)
+    return out, seen_img
+
+
 # ------------------------------------------------------------------ geometry maps of a rendered frame (DESIGN.md section 7k)
 GBUFFER_PANELS = ('depth', 'normal', 'shaded')
 GBUFFER_MAX_PIXELS = 1 << 31

@@ -8,7 +8,8 @@ seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on dis
 <...>/<load_net>/mesh/mesh.ply and mesh.json; with `mesh_pose.frames` also mesh/posed/<frame name>.ply and mesh/posed.json;
 with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json; with `mesh_rig.enable True`
 also mesh/rigged.glb, the mesh with a skeleton, skin weights and the motion of `mesh_rig.frames`, and mesh/rig.json; with
-`mesh_texture.enable True` also mesh/texture.png, the model's colour on a per-triangle atlas of the mesh (run_mesh below).
+`mesh_texture.enable True` also mesh/texture.png, the model's colour on a per-triangle atlas of the mesh; with
+`mesh_photo.enable True` also mesh/texture_photo.png, the dataset's photographs projected onto that atlas (run_mesh below).
 `show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
 `geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
 `--type animate animate.motion PATH` drives the subject of a prepared dataset with a motion it has not seen (occnerf_amd/
@@ -290,6 +291,10 @@ def run_mesh():
     mesh_texture.enable, also the model's colour baked into a per-triangle atlas of the kept mesh (occnerf_amd/mesh.py
     export_texture) -> mesh/texture.png and texture.json; the image replaces the vertex colours in
     rigged.glb, without the rig it goes into a static mesh/textured.glb, and every mesh_view panel gains a textured render.
+    With mesh_photo.enable as well (a prepared dataset only), also the photographs of mesh_photo.frames projected onto that atlas
+    (occnerf_amd/mesh.py export_photo_texture) -> mesh/texture_photo.png (what the frames saw, the colour
+    field elsewhere), texture_seen.png (how many frames saw each texel) and texture_photo.json; with mesh_photo.in_glb the
+    glTF files carry that image, and every mesh_view panel gains a photo-textured render.
     Rank 0 alone works."""
     from occnerf_amd.mesh import MeshPoser, PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
@@ -321,6 +326,17 @@ def run_mesh():
         if texturing:
             from occnerf_amd.mesh import check_texture
             mtex = check_texture(mtex)
+        mph = cfg.get('mesh_photo') or {}
+        photographing = bool(mph.get('enable', False))
+        if photographing:
+            from occnerf_amd.mesh import check_photo
+            mph = check_photo(mph)
+            if not texturing:
+                raise SystemExit('mesh_photo.enable: the photographs are blended into the atlas of mesh_texture.enable, which is '
+                                 'not set')
+            if resolve_dataset_path(cfg, 'movement') is None:
+                raise SystemExit('mesh_photo.enable: the photographs and masks are those of a prepared dataset; the synthetic '
+                                 'frame source has none (set train.dataset_path or movement.dataset)')
         kept = {} if posing or viewing or rigging or texturing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
                            normals=bool(m.normals), chunk=int(m.chunk), keep=kept, components=m.get('components', 'all'),
@@ -337,13 +353,33 @@ def run_mesh():
             tex = export_texture(model, out_dir, kept, mtex, chunk=int(m.chunk))
             print(f"texture: {tex['texels_queried']} texels of {tex['triangles']} triangles in cells of {tex['n']} -> "
                   f"{os.path.join(out_dir, 'texture.png')} ({tex['W']} x {tex['H']}, {100.0 * tex['unowned_share']:.1f} % unowned)")
-            if not rigging:
+            if not rigging and not photographing:
                 size = export_textured(out_dir, kept, normals=bool(m.normals))
                 print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
-        if posing or rigging or viewing:
+        if posing or rigging or viewing or photographing:
             cfg.ignore_non_rigid_motions = ignore_non_rigid
             solver = dict(candidates=int(mp.get('candidates', 3)), max_iter=int(mp.get('max_iter', 20)),
                           tol=float(mp.get('tol', 1e-7)), non_rigid=bool(mp.get('non_rigid', True)), iter_val=cfg.eval_iter)
+        if viewing or photographing:
+            # the dataset as --type movement opens it, so K, the mask and the photograph are those of the training size, and a
+            # poser of its own, which keeps nothing unless two exports ask for its frames (the dataset's frames are not the
+            # indices of the source below)
+            from occnerf_amd.dataset import PreparedDataset
+            dev = torch.device('cuda', torch.cuda.current_device())
+            dataset = PreparedDataset.from_cfg(cfg, resolve_dataset_path(cfg, 'movement'), device=None, prepare_device=dev)
+            view_poser = MeshPoser(model, kept['verts'], keep=viewing and photographing, **solver)
+        if photographing:
+            # the photographs on the atlas: what the frames saw, the colour field elsewhere
+            from occnerf_amd.mesh import export_photo_texture, export_textured
+            ph = export_photo_texture(model, out_dir, kept, dataset, mph, poser=view_poser)
+            print(f"photo texture: {len(ph['frames'])} frames, {100.0 * ph['seen_share']:.1f} % of {ph['owned_texels']} texels seen at "
+                  f"least once (depth bias {ph['bias_m']:g} m) -> {os.path.join(out_dir, 'texture_photo.png')}")
+            glb_texture = kept['texture_photo'] if mph['in_glb'] else kept['texture']
+            if not rigging:
+                size = export_textured(out_dir, {**kept, 'texture': glb_texture}, normals=bool(m.normals))
+                print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
+        elif texturing:
+            glb_texture = kept['texture']
         if posing or rigging:
             # the movement source's body constants only, and one poser over them: a frame both
             # mesh_pose.frames and mesh_rig.frames name is solved once
@@ -360,7 +396,7 @@ def run_mesh():
             # the kept mesh with a skeleton, skin weights and the frames' motion as one glTF
             from occnerf_amd.mesh import export_rig
             rigged = export_rig(model, out_dir, kept, source, mrig, normals=bool(m.normals), poser=poser,
-                                **({'texture': kept['texture']} if texturing else {}))
+                                **({'texture': glb_texture} if texturing else {}))
             print(f"rig: {rigged['vertices']} vertices with up to {rigged['K']} joints each ({rigged['bound_to_root_for_want_of_a_bone']} "
                   f"bound to the root for want of a bone), {len(rigged['frames'])} keys -> {os.path.join(out_dir, 'rigged.glb')} "
                   f"({rigged['bytes']} bytes)")
@@ -372,16 +408,11 @@ def run_mesh():
         if viewing:
             # the posed mesh through each frame's own camera, against the frame's mask: the dataset as
             # --type movement opens it, so K, the mask and the photograph are those of the training size
-            from occnerf_amd.dataset import PreparedDataset
             from occnerf_amd.mesh_view import export_views
-            dev = torch.device('cuda', torch.cuda.current_device())
-            dataset = PreparedDataset.from_cfg(cfg, resolve_dataset_path(cfg, 'movement'), device=None, prepare_device=dev)
-            # (a poser of its own, which keeps nothing: the dataset's frames are not the indices of the source above; that
-            # one's kept frames go first)
-            poser = MeshPoser(model, kept['verts'], keep=False, **solver)
             views = export_views(model, out_dir, kept, dataset, mv.frames, panels=bool(mv.get('panels', True)), bgcolor=cfg.bgcolor,
-                                 poser=poser,
-                                 **({'texture': kept['texture']} if texturing else {}))
+                                 poser=view_poser,
+                                 **({'texture': kept['texture']} if texturing else {}),
+                                 **({'photo': kept['texture_photo']} if photographing else {}))
             for f in views['frames']:
                 iou = 'none (empty union)' if f['iou'] is None else f"{f['iou']:.4f}"
                 print(f"view {f['name']}: IoU {iou} ({f['intersection']} / {f['union']} pixels), {f['covered']} pixels covered, "
