@@ -233,13 +233,11 @@ def _autograd(c, dtype):
     return raw.grad.double().numpy(), mask.grad.double().numpy()
 
 
-def composite_backward_float64(c):
-    """c: a case of tests/step_backward_cases.py (fp32 arrays raw [n,S,5], mask, z [n,S], rays8, bg [3], g_rgb, g_acc, g_depth)
-    -> dict d_raw [n,S,5], d_mask [n,S] (float64 autograd), B_raw, B_mask (condition weights), E_raw, E_mask (error weights), floor_raw, floor_mask (absolute terms)."""
-    d_raw, d_mask = _autograd(c, torch.float64)
+def composite_running_weights(c):
+    """The float64 forward of a case and its first-order running error weights, in units of u (module docstring): dict of
+    [n, S] arrays dist, sp, dsp, em, alpha, tt, T, w, e_s, a_s, t_s, tau_s, om_s, and col [n, S, 3].  The forward compositor's
+    per-entry check (tests/composite_forward_restatement.py) builds its weights from the same a_s, t_s, tau_s, om_s."""
     raw, mask, z = (np.asarray(c[k], np.float64) for k in ('raw', 'mask', 'z'))
-    g_rgb, g_acc, g_dep = (np.asarray(c[k], np.float64) for k in ('g_rgb', 'g_acc', 'g_depth'))
-    bg = np.asarray(c['bg'], np.float64)
     n, S = z.shape
     dn = np.linalg.norm(np.asarray(c['rays8'], np.float64)[:, 3:6], axis=1)
     dist = np.concatenate([z[:, 1:] - z[:, :-1], np.full((n, 1), 1e10)], 1) * dn[:, None]
@@ -253,6 +251,28 @@ def composite_backward_float64(c):
     tt = 1.0 - alpha + 1e-10
     T = np.concatenate([np.ones((n, 1)), np.cumprod(tt, 1)[:, :-1]], 1)
     w = alpha * T
+    aT, att = np.abs(T), np.abs(tt)
+    e = em * (1.0 + sp * dist)                                                  # |d em|: exp's own ulp and its argument's
+    a = np.abs(alpha) + np.abs(mask) * e                                        # |d alpha|
+    t = a + att                                                                 # |d tt|
+    step = t / att + 1.0
+    tau = np.concatenate([np.zeros((n, 1)), np.cumsum(step, 1)[:, :-1]], 1)     # |d T| / |T|
+    omega = a * aT + np.abs(alpha) * aT * tau + np.abs(w)                       # |d w|
+    return {'dist': dist, 'sp': sp, 'dsp': dsp, 'em': em, 'col': col, 'alpha': alpha, 'tt': tt, 'T': T, 'w': w, 'e_s': e, 'a_s': a,
+            't_s': t, 'tau_s': tau, 'om_s': omega}
+
+
+def composite_backward_float64(c):
+    """c: a case of tests/step_backward_cases.py (fp32 arrays raw [n,S,5], mask, z [n,S], rays8, bg [3], g_rgb, g_acc, g_depth)
+    -> dict d_raw [n,S,5], d_mask [n,S] (float64 autograd), B_raw, B_mask (condition weights), E_raw, E_mask (error weights), floor_raw, floor_mask (absolute terms)."""
+    d_raw, d_mask = _autograd(c, torch.float64)
+    mask, z = (np.asarray(c[k], np.float64) for k in ('mask', 'z'))
+    g_rgb, g_acc, g_dep = (np.asarray(c[k], np.float64) for k in ('g_rgb', 'g_acc', 'g_depth'))
+    bg = np.asarray(c['bg'], np.float64)
+    n, S = z.shape
+    rw = composite_running_weights(c)
+    dist, sp, dsp, em, col, alpha, tt, T, w = (rw[k] for k in ('dist', 'sp', 'dsp', 'em', 'col', 'alpha', 'tt', 'T', 'w'))
+    e, a, t, tau, omega = (rw[k] for k in ('e_s', 'a_s', 't_s', 'tau_s', 'om_s'))
     Gh = (np.abs(g_rgb[:, None, :] * col).sum(-1) + np.abs(g_dep[:, None] * z) + np.abs(g_acc)[:, None]
           + (np.abs(g_rgb * bg[None, :]).sum(-1) / 255.0)[:, None])
     gw = Gh * np.abs(w)
@@ -264,12 +284,6 @@ def composite_backward_float64(c):
     B_raw[..., 3] = D * lin * em
     # E: the first-order rounding-error weight (see the module docstring), in units of u
     aT, aw, att = np.abs(T), np.abs(w), np.abs(tt)
-    e = em * (1.0 + sp * dist)                                                  # |d em|: exp's own ulp and its argument's
-    a = np.abs(alpha) + np.abs(mask) * e                                        # |d alpha|
-    t = a + att                                                                 # |d tt|
-    step = t / att + 1.0
-    tau = np.concatenate([np.zeros((n, 1)), np.cumsum(step, 1)[:, :-1]], 1)     # |d T| / |T|
-    omega = a * aT + np.abs(alpha) * aT * tau + aw                              # |d w|
     go = Gh * omega + (S + 4.0) * gw
     dR = np.flip(np.cumsum(np.flip(go, 1), 1), 1) - go                          # |d R|: sum over j > s
     dda = Gh * aT * (3.0 + tau) + dR / att + tail / att * (1.0 + t / att)       # |d dalpha|
