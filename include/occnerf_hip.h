@@ -977,6 +977,46 @@ int occnerf_mesh_texture_project(const int32_t *xy, const double *z, const uint8
 int occnerf_mesh_texture_blend(const int64_t *acc, const int32_t *seen, int64_t T, int32_t n, int32_t C, int32_t H, int32_t W,
                                int32_t min_seen, uint8_t *atlas, uint8_t *seen_img, void *stream);
 
+/* The tangent-space normal map of the exported mesh (occnerf_amd/mesh.py bake_normal_map, run.py --type mesh mesh_normal.enable;
+ * DESIGN.md section 7q).  The reference has no counterpart of these two entries.  Bit-identical to
+ * tests/mesh_normal_restatement.py (fp64 on the float32 inputs, one rounding per operator, + - * / sqrt floor rint only); no
+ * atomics, the same bytes on every run. */
+
+/* No counterpart in the reference.  One thread per owned texel of the atlas of occnerf_mesh_texture_fill's layout.  verts[V,3],
+ * vnormals[V,3] float32 (the mesh's area-weighted vertex normals), faces[T,3] int32, tangents[T,3,4] float32 and creased[T] uint8
+ * (mesh.corner_tangents), pts[T P,3] float32 (occnerf_mesh_texel_points), field[nz,ny,nx] float32 with grid point (i,j,k) at
+ * h_lo + (i,j,k) h_f (HOST h_lo[3] double), level the iso-value.  Per texel with numerators (b0, b1, b2) = (m - i' - j', i', j'):
+ * nh = normalise((b0 N0 + b1 N1) + b2 N2), the face normal and flag 8 when that sum is zero or not finite;
+ * f(q) = the trilinear sample at (q - lo) / h_f clamped to [0, n_a - 1], cell min(floor, n_a - 2), x then y then z, each blend
+ * a (1 - f) + b f; u_k = f(p + (k delta) nh) - level for k = -S .. S with delta = h_f / 2; a crossing between k and k + 1 where
+ * (u > 0) differs and both are finite, s = (k + u_k / (u_k - u_k+1)) delta, the smallest |s| wins, a tie goes to the positive
+ * one, none: s = 0 and flag 1; q = p + s nh; g_a = f(q + h_f e_a) - f(q - h_f e_a), N_f = -g / sqrt((gx gx + gy gy) + gz gz),
+ * nh and flag 2 when that sum is zero or not finite; Th = normalise of the blended corner tangents, B = nh x Th,
+ * (tx, ty, tz) = the solution of tx Th + ty B + tz nh = N_f by cofactors, normalised; |det| < 2^-20, a non-finite solution,
+ * tz <= 0 or creased[t] give (0, 0, 1) and flag 4.  atlas[H,W,3] uint8, IN/OUT, receives rint(127.5 (c + 1)) clamped to
+ * 0..255 at the texel's place, every other byte stays; offset[T P] float32 = s, flags[T P] uint8, normal[T P,3] float32 = N_f
+ * (a NaN is stored as 0x7FC00000).  A face with an index outside [0, V): offset and normal NaN, flags 0, the flat bytes, and
+ * status[0] (int32, zeroed by the caller) becomes 1; no such index is used as an address.  Refused: a null pointer, n outside
+ * 4..64, T P >= 2^31, an atlas that does not hold T triangles, a grid axis below 2 or 2^31 points, S outside 1..64, h_f not
+ * positive and finite.  T = 0 returns 0 without a launch. */
+int occnerf_mesh_normal_bake(const float *verts, const float *vnormals, int64_t V, const int32_t *faces, int64_t T,
+                             const float *tangents, const uint8_t *creased, const float *pts, int32_t n, int32_t C, int32_t H,
+                             int32_t W, const float *field, int32_t nx, int32_t ny, int32_t nz, const double *h_lo, double h_f,
+                             float level, int32_t S, uint8_t *atlas, float *offset, uint8_t *flags, float *normal,
+                             int32_t *status, void *stream);
+/* No counterpart in the reference.  The lit twin of occnerf_mesh_resolve_textured: keys[Himg*Wimg] of occnerf_mesh_raster ->
+ * shade_geometry, shade_mapped [Himg*Wimg,3] uint8, both in one launch.  A hit pixel: the winner t and its weights (w0, w1, w2)
+ * as occnerf_mesh_resolve_textured forms them; Nh = normalise((w0 N0 + w1 N1) + w2 N2) of vnormals[V,3] float32 (the posed
+ * mesh's), Th likewise of tangents[T,3,4] float32, B = Nh x Th; the normal atlas[aH,aW,3] through that entry's sampler with the
+ * fp64 blend s kept unrounded, c = s / 127.5 - 1, nm = normalise((cx Th + cy B) + cz Nh), but Nh itself where all four taps are
+ * the flat code (128, 128, 255); d = M (column, row, 1) with the HOST h_M[9] double, row major; the grey byte is
+ * uint8(255.0f * clamp01(float32(-(n.d) / sqrt(d.d)))) with NaN -> 0, from Nh in shade_geometry and from nm in shade_mapped.
+ * Every other pixel: the HOST h_bgcolor[3] uint8.  T = 0 or V = 0: the background everywhere. */
+int occnerf_mesh_resolve_lit(const uint64_t *keys, const int32_t *faces, int64_t T, int64_t V, const int32_t *xy,
+                             const double *z, int32_t Himg, int32_t Wimg, const float *vnormals, const float *tangents,
+                             const uint8_t *atlas, int32_t aH, int32_t aW, int32_t n, int32_t C, const double *h_M,
+                             const uint8_t *h_bgcolor, uint8_t *shade_geometry, uint8_t *shade_mapped, void *stream);
+
 /* Collapsed samples, classified once in front of the kNN and feature kernels (no counterpart in the
  * reference).  One lane per entry o of the live list rows[0 .. *n_dev) (capacity N_max): flag[o] = 1 iff xyz[rows[o]] lies
  * inside the radius of center[4] (the |p - c|^2 < r^2 test of the kNN and feature kernels) AND the encoder input x[4] the

@@ -159,6 +159,9 @@ SIGNATURES = {
     'occnerf_mesh_resolve_textured': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     'occnerf_mesh_texture_project': (C.c_int, [_vp] * 5 + [_i64, _vp, _i64, _i32] + [_vp] * 5 + [_i32, _i32, C.c_double] + [_vp] * 5),
     'occnerf_mesh_texture_blend': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    'occnerf_mesh_normal_bake': (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp,
+                                           C.c_double, _f32, _i32] + [_vp] * 6),
+    'occnerf_mesh_resolve_lit': (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32] + [_vp] * 5),
     'occnerf_center_classify': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp]),
     'occnerf_center_split_temp_bytes': (_i64, [_i64]),
     'occnerf_center_split': (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -162,6 +162,12 @@ _DEFAULTS = {
     # the frames that must have seen a texel before their mean replaces the field's colour; in_glb: the photo atlas goes into
     # rigged.glb / textured.glb in place of texture.png
     'mesh_photo': {'enable': False, 'frames': 'all', 'bias': None, 'min_seen': 1, 'in_glb': True},
+    # run.py --type mesh, a tangent-space normal map of the density field on the atlas (occnerf_amd/mesh.py export_normal_map,
+    # DESIGN.md section 7q; needs mesh_texture.enable): enable writes mesh/texture_normal.png and texture_normal.json;
+    # resolution: the voxels along the longest axis of the fine density grid the detail is read from (None:
+    # max(256, mesh.resolution)); cage: how far in metres a texel may lie from that grid's surface (None: the mesh's voxel
+    # edge); in_glb: rigged.glb / textured.glb carry TANGENT and the map as materials[0].normalTexture (needs mesh.normals)
+    'mesh_normal': {'enable': False, 'resolution': None, 'cage': None, 'in_glb': True},
     # run.py --type mesh, the posed mesh seen from its frame's camera (occnerf_amd/mesh_view.py export_views, DESIGN.md section
     # 7j): frames = None (nothing happens), a list of frame indices of the movement source's prepared dataset, or 'all'; per
     # frame the silhouette's IoU with the frame's mask goes to mesh/view.json; panels: also write mesh/view/<frame name>.png, the

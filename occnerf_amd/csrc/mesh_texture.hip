@@ -19,34 +19,10 @@
 // entry has checked against the atlas' size.  The empty key, the image-size test, the background and the byte store are
 // mesh_screen.h's, shared with mesh_raster.hip's resolve.
 #include "common.h"
+#include "mesh_atlas.h"
 #include "mesh_screen.h"
 
 namespace occ {
-
-constexpr int kTexThreads = 256;
-constexpr int kTexMinCell = 4;
-constexpr int kTexMaxCell = 64;
-constexpr int kTexMaxSide = 16384;
-
-// Texel k of a triangle -> (i', j') in its own frame: row j' holds the n - 1 - j' texels i' = 0 .. n - 2 - j'.
-__device__ __forceinline__ void texel_of(int k, int n, int &i, int &j) {
-    int row = n - 1;
-    j = 0;
-    while (k >= row) {              // at most n - 2 <= 62 steps
-        k -= row;
-        row--;
-        j++;
-    }
-    i = k;
-}
-
-// (column, row) in the atlas of texel (i', j') of triangle t.
-__device__ __forceinline__ void atlas_of(int64_t t, int i, int j, int n, int C, int &x, int &y) {
-    const int64_t c = t >> 1;
-    const bool odd = (t & 1) != 0;
-    x = (int)(c % C) * n + (odd ? n - 1 - i : i);
-    y = (int)(c / C) * n + (odd ? n - 1 - j : j);
-}
 
 __global__ __launch_bounds__(kTexThreads) void mesh_texel_points_kernel(const float *__restrict__ verts, int64_t V,
                                                                         const int32_t *__restrict__ faces, int64_t T, int n, int P,
@@ -150,13 +126,6 @@ __global__ __launch_bounds__(kTexThreads) void mesh_resolve_textured_kernel(
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) rgb[pix * 3 + c] = out[c];
-}
-
-// The cells of T triangles fit an atlas of C cells per row and H rows of texels.
-inline bool tex_layout_ok(int64_t T, int32_t n, int32_t C, int32_t H, int32_t W) {
-    if (C < 1 || W != (int64_t)C * n || H < 1 || H > kTexMaxSide || W > kTexMaxSide) return false;
-    const int64_t cells = (T + 1) / 2, rows = (cells + C - 1) / C;
-    return rows * n <= H;
 }
 
 // ---------------------------------------------------------------- the photographs on the atlas

@@ -6,7 +6,8 @@ the world placement; one morph target per key with a STEP weights channel).  The
 rotated to glTF's +Y-up convention and nothing is rescaled.  The same inputs give the same bytes: no date, no host name, JSON
 with sorted keys.  With texture= the primitive is unwelded (three vertices per triangle, TEXCOORD_0 into the per-triangle atlas of
 DESIGN.md section 7o, no COLOR_0) and carries one PNG image, one sampler, one texture and one material; with joints=None the mesh
-is static.  Normal maps, several materials, cameras and several scenes are not written."""
+is static; with texture['normal_png'] / ['tangents'] it also carries TANGENT and a tangent-space normal map.
+Several materials, cameras and several scenes are not written."""
 import json
 import struct
 
@@ -96,7 +97,10 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
     texture: None or {'uv': float32 [T,3,2] (mesh.texture_uv), 'png': the atlas as the bytes of a PNG file}: every per-vertex
     array is gathered by faces.reshape(-1), the indices are 0 .. 3T-1, TEXCOORD_0 replaces COLOR_0 (viewers multiply the two;
     colors may be None) and the image travels inside the binary chunk.  Without texture and with joints the bytes are those
-    written before either was offered."""
+    written before either was offered.  texture may also carry 'normal_png' (the tangent-space normal map of DESIGN.md section
+    7q on the same atlas, a PNG file) and 'tangents' float32 [T,3,4] (mesh.corner_tangents; normals must be given): TANGENT is a
+    float32 VEC4 per corner, a second image and texture share the sampler and materials[0].normalTexture names it; morph
+    targets carry no tangent deltas.  Without the two keys the bytes are those written before they were offered."""
     verts = np.asarray(verts, dtype='<f4').reshape(-1, 3)
     faces = np.asarray(faces, dtype='<i4').reshape(-1, 3)
     V = verts.shape[0]
@@ -120,6 +124,15 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
         if uv.shape != (faces.shape[0], 3, 2) or png[:8] != b'\x89PNG\r\n\x1a\n':
             raise RuntimeError(f"write_glb: texture['uv'] must be float32 [{faces.shape[0]},3,2] and texture['png'] a PNG file, got "
                                f'{uv.shape} and {len(png)} bytes')
+        if ('normal_png' in texture) != ('tangents' in texture):
+            raise RuntimeError("write_glb: texture['normal_png'] and texture['tangents'] go together: a normal map needs its tangents")
+        if 'normal_png' in texture:
+            normal_png, tangents = bytes(texture['normal_png']), np.asarray(texture['tangents'], dtype='<f4')
+            if tangents.shape != (faces.shape[0], 3, 4) or normal_png[:8] != b'\x89PNG\r\n\x1a\n':
+                raise RuntimeError(f"write_glb: texture['tangents'] must be float32 [{faces.shape[0]},3,4] and texture['normal_png'] a "
+                                   f'PNG file, got {tangents.shape} and {len(normal_png)} bytes')
+            if normals is None:
+                raise RuntimeError("write_glb: a normal map needs normals: glTF's TANGENT is read against NORMAL")
     fps = float(fps)
     if not (0.0 < fps < float('inf')):
         raise RuntimeError(f'write_glb: fps = {fps} must be a positive finite number')
@@ -144,6 +157,9 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
     attributes = {'POSITION': buf.add(verts, FLOAT, 'VEC3', ARRAY_BUFFER, minmax=True)}
     if normals is not None:
         attributes['NORMAL'] = buf.add(normals, FLOAT, 'VEC3', ARRAY_BUFFER)
+    mapped = texture is not None and 'normal_png' in texture
+    if mapped:                                           # per corner already: a row per vertex of the unwelded primitive
+        attributes['TANGENT'] = buf.add(tangents.reshape(-1, 4), FLOAT, 'VEC4', ARRAY_BUFFER)
     if texture is None:
         rgba = np.concatenate([colors, np.full((V, 1), 255, np.uint8)], 1)
         attributes['COLOR_0'] = buf.add(rgba, UBYTE, 'VEC4', ARRAY_BUFFER, normalized=True)
@@ -161,6 +177,10 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
         buf.blob.extend(png)
         image_view = len(buf.views) - 1
         primitive['material'] = 0
+        if mapped:
+            buf.blob.extend(b'\0' * (-len(buf.blob) % 4))
+            buf.views.append({'buffer': 0, 'byteOffset': len(buf.blob), 'byteLength': len(normal_png)})
+            buf.blob.extend(normal_png)
     if correctives is not None:
         d = np.asarray(correctives, dtype='<f4')
         primitive['targets'] = [{'POSITION': buf.add(d[f], FLOAT, 'VEC3', ARRAY_BUFFER, minmax=True)} for f in range(F)]
@@ -172,6 +192,10 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, normals=No
                   'textures': [{'sampler': 0, 'source': 0}],
                   'materials': [{'name': 'baked', 'pbrMetallicRoughness': {'baseColorTexture': {'index': 0}, 'metallicFactor': 0.0,
                                                                           'roughnessFactor': 1.0}}]}
+        if mapped:                                       # a second image and texture on the one sampler
+            extras['images'].append({'bufferView': image_view + 1, 'mimeType': 'image/png'})
+            extras['textures'].append({'sampler': 0, 'source': 1})
+            extras['materials'][0]['normalTexture'] = {'index': 1}
     else:
         extras = {}
     if not rigged:

@@ -30,11 +30,17 @@ counterpart there.
                  posed mesh's texels through the frame's camera, tested against the rasteriser's depth keys and the frame's
                  mask and summed in integers (csrc/mesh_texture.hip mesh_texture_project / mesh_texture_blend) ->
                  texture_photo.png (the frames' weighted mean where a frame saw the texel, the colour field elsewhere),
-                 texture_seen.png (how many frames saw each texel) and texture_photo.json.
+                 texture_seen.png (how many frames saw each texel) and texture_photo.json;
+  check_normal, corner_tangents, bake_normal_map, export_normal_map
+                 a tangent-space normal map on that atlas (mesh_normal.enable): a fine density grid is
+                 the detail source, every texel is projected along the interpolated vertex normal onto its iso-surface and the
+                 field's normal there is stored in the frame of the vertex normals and the per-corner tangents
+                 (csrc/mesh_normal.hip) -> texture_normal.png, texture_normal.json, TANGENT and normalTexture in the glTF files.
 
 Every step is a pure function of its inputs: the same checkpoint and settings give the same PLY byte for byte (the sidecars
 differ in their wall times only).  Decimation, smoothing, hole filling, OBJ, a mesh welded from the f16x3 kernels' field,
-area-proportional or merged texture charts, mip-safe padding and normal maps are not offered; nor, for the posed mesh, roots of
+area-proportional or merged texture charts, mip-safe padding, object-space normal maps, displacement or occlusion maps (the
+normal map's offsets are only reported) and MikkTSpace tangents are not offered; nor, for the posed mesh, roots of
 the warp other than the owning bone's or changes of topology; nor, for the photo texture, a robust blend (median, best frame),
 exposure compensation between frames, the all_cameras.pkl rig, a pose refined against the photograph or anything that repairs a
 wrong mask."""
@@ -258,7 +264,7 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
                 components='all', drop_cavities=False):
     """<out_dir>/mesh.ply and mesh.json of the canonical body -> the sidecar's dict.  keep: a dict that receives what
     export_posed needs of the mesh ('verts' float32 [V,3] on the device, 'faces' int32 [T,3] and 'colors' uint8 [V,3] numpy, 'h'
-    the voxel edge).
+    the voxel edge, 'level' the float32 level).
     components / drop_cavities: the clean-up of DESIGN.md section 7m; at their defaults nothing is labelled and the files are
     those written without them.  Otherwise the colours, the normals and `keep` are those of the kept mesh, and the sidecar
     gains 'components', 'extracted_vertices' / 'extracted_triangles' and seconds['components']."""
@@ -288,7 +294,7 @@ def export_mesh(net, out_dir, bbox_min, bbox_max, resolution=256, level=None, no
                       f'{float(np.float32(used)):g}): the mesh is open there and is written as it is')
     v, f = verts.cpu().numpy(), faces.cpu().numpy()
     if keep is not None:
-        keep.update(verts=verts, faces=f, colors=colors, h=h)
+        keep.update(verts=verts, faces=f, colors=colors, h=h, level=float(np.float32(used)))
     os.makedirs(out_dir, exist_ok=True)
     write_ply(os.path.join(out_dir, 'mesh.ply'), v, f, colors, _normals(v, f, normals))
     info = {'resolution': int(resolution), 'h': h, 'level': float(np.float32(used)), 'level_is_default': level is None,
@@ -618,7 +624,7 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
         animation={'rotation': keys['rotation'], 'translation': keys['translation']} if F else None,
         world={'rotation': keys['world_rotation'], 'translation': keys['world_translation']} if F and rig['world'] else None,
         correctives=delta.cpu().numpy() if correct and F else None, fps=float(rig['fps']),
-        **({} if texture is None else {'texture': {'uv': texture['uv'], 'png': texture['png']}}))
+        **({} if texture is None else {'texture': _glb_texture(texture)}))
     t4 = time.perf_counter()
     n, share = count.cpu().numpy(), kept_share.cpu().numpy().astype(np.float64)
     bound = share[n > 0]
@@ -636,6 +642,8 @@ def export_rig(net, out_dir, kept, source, rig=None, candidates=3, max_iter=20, 
                         'report': round(t3 - t2 - t_pose - t_lbs, 4), 'write': round(t4 - t3, 4)}}
     if texture is not None:
         info.update(textured=True, unwelded_vertices=3 * int(len(faces)))
+        if 'normal_png' in texture:
+            info.update(normal_mapped=True)
     _write_sidecar(os.path.join(out_dir, 'rig.json'), info)
     return info
 
@@ -748,7 +756,178 @@ def export_textured(out_dir, kept, normals=True):
     from . import gltf
     v, faces, tex = kept['verts'].cpu().numpy(), kept['faces'], kept['texture']
     return gltf.write_glb(os.path.join(out_dir, 'textured.glb'), v, faces, None, None, None, None,
-                          normals=_normals(v, faces, normals), texture={'uv': tex['uv'], 'png': tex['png']})
+                          normals=_normals(v, faces, normals), texture=_glb_texture(tex))
+
+
+def _glb_texture(texture):
+    """What gltf.write_glb takes of a kept texture: the colour image and, where with_normal_map has put one in, the normal map."""
+    return {k: texture[k] for k in ('uv', 'png', 'normal_png', 'tangents') if k in texture}
+
+
+def with_normal_map(texture, normal):
+    """The kept colour texture (kept['texture'] or kept['texture_photo']) with the normal map of kept['texture_normal'] beside
+    it, for export_rig and export_textured: the two share the atlas' layout and TEXCOORD_0."""
+    if int(texture['n']) != int(normal['n']) or int(texture['C']) != int(normal['C']):
+        raise RuntimeError(f"mesh_normal: the normal map's cells ({normal['n']}, {normal['C']} per row) are not the colour atlas' "
+                           f"({texture['n']}, {texture['C']} per row)")
+    return {**texture, 'normal_png': normal['png'], 'tangents': normal['tangents']}
+
+
+# ------------------------------------------------------------------ the normal map of the exported mesh (DESIGN.md section 7q)
+NORMAL_DEFAULTS = {'enable': False, 'resolution': None, 'cage': None, 'in_glb': True}
+NORMAL_MIN_RESOLUTION = 256
+
+
+def check_normal(normal):
+    """The mesh_normal keys as export_normal_map takes them (a dict with every key of NORMAL_DEFAULTS); a value out of range is
+    refused by name.  resolution None: max(256, mesh.resolution); cage None: the mesh's own voxel edge."""
+    normal = {k: (normal.get(k, v) if hasattr(normal, 'get') else v) for k, v in NORMAL_DEFAULTS.items()}
+    for key in ('enable', 'in_glb'):
+        if not isinstance(normal[key], (bool, np.bool_)):
+            raise RuntimeError(f'mesh_normal.{key} = {normal[key]!r}: True or False')
+    res = normal['resolution']
+    if res is not None:
+        if isinstance(res, (bool, np.bool_)) or not isinstance(res, (int, np.integer)) or not 1 <= int(res) <= 2048:
+            raise RuntimeError(f'mesh_normal.resolution = {res!r}: None (max({NORMAL_MIN_RESOLUTION}, mesh.resolution)) or a whole '
+                               'number of voxels along the longest axis of the box in 1..2048')
+        normal['resolution'] = int(res)
+    cage = normal['cage']
+    if cage is not None:
+        if isinstance(cage, (bool, np.bool_)) or not isinstance(cage, (int, float, np.integer, np.floating)) or \
+                not 0.0 < float(cage) < float('inf'):
+            raise RuntimeError(f'mesh_normal.cage = {cage!r}: None (the voxel edge of the mesh) or a positive finite number of metres')
+        normal['cage'] = float(cage)
+    return normal
+
+
+def corner_tangents(verts, faces, normals, n=None):
+    """(tangents float32 [T,3,4], creased bool [T]) of the mesh verts float32 [V,3] / faces int32 [T,3] with the float32 vertex
+    normals the file carries, on the host in float64: with e1 = v1 - v0, e2 = v2 - v0 and sigma = +1 for
+    an even triangle, -1 for an odd one -- in the per-triangle chart of texture_uv the column grows along sigma e1 and the row
+    along sigma e2 --, T_c = normalise(sigma e1 - N_c ((N_c . sigma e1) / (N_c . N_c))) and w = +1.  A triangle with a corner whose vertex normal
+    does not lie on the face's front side (N_c . (e1 x e2) <= 0), a zero e1 x e2 or a zero or non-finite T_c is creased: its
+    tangents are (1, 0, 0, 1) and the bake gives it the flat normal.  n (the cell edge) does not enter: the chart's axes are
+    parallel to e1 and e2 at every n."""
+    v = np.asarray(verts, dtype=np.float32).astype(np.float64).reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    N = np.asarray(normals, dtype=np.float32).astype(np.float64).reshape(-1, 3)[f]
+    T = f.shape[0]
+
+    def dot(a, b):
+        return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+    big = np.finfo(np.float64).max
+    e1, e2 = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+    se1 = (np.where(np.arange(T) % 2 == 0, 1.0, -1.0)[:, None] * e1)[:, None, :]
+    with np.errstate(all='ignore'):
+        t = se1 - N * (dot(N, se1) / dot(N, N))[..., None]
+        l2 = dot(t, t)
+        ok = (l2 > 0.0) & (l2 <= big)
+        t = np.where(ok[..., None], t / np.sqrt(np.where(ok, l2, 1.0))[..., None], t)
+        fn = np.stack([e1[:, 1] * e2[:, 2] - e1[:, 2] * e2[:, 1], e1[:, 2] * e2[:, 0] - e1[:, 0] * e2[:, 2],
+                       e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]], -1)
+        front = dot(N, fn[:, None, :]) > 0.0
+        a2 = dot(fn, fn)
+        creased = ~(front.all(1) & ok.all(1) & (a2 > 0.0) & (a2 <= big))
+    out = np.concatenate([t, np.ones((T, 3, 1))], -1)
+    out[creased] = [1.0, 0.0, 0.0, 1.0]
+    return out.astype(np.float32), creased
+
+
+def bake_normal_map(net, verts, faces, n, level, bbox_min, bbox_max, resolution, cage, chunk=1 << 21):
+    """(atlas uint8 [H,W,3], offsets float32 [T,P], flags uint8 [T,P], stats) on the device: the tangent-space normal map of the
+    mesh verts float32 [V,3] (device) / faces int32 [T,3] on the atlas of cell edge n.  A density grid of
+    `resolution` voxels along the longest axis of the box is computed anew (density_grid); every texel point
+    (ops.mesh_texel_points) is projected along the interpolated vertex normal onto that grid's surface at `level`, at most `cage`
+    metres away, and the field's normal there is stored in the frame of the vertex normals and corner_tangents
+    (ops.mesh_normal_bake).  stats['tangents'] / ['creased'] / ['normals'] are the host arrays the glTF carries."""
+    dev = verts.device
+    f_np = np.ascontiguousarray(np.asarray(faces.cpu().numpy() if torch.is_tensor(faces) else faces, dtype=np.int32).reshape(-1, 3))
+    T, n = int(f_np.shape[0]), int(n)
+    if T == 0 or int(verts.shape[0]) == 0:
+        raise RuntimeError(f'mesh_normal: the mesh has {int(verts.shape[0])} vertices and {T} triangles: there is nothing to bake '
+                           '(on a checkpoint without a surface at the default level set mesh.level)')
+    C, R, W, H, P = atlas_layout(T, n)
+    h_f, shape = grid_shape(bbox_min, bbox_max, resolution)
+    S = ops.mesh_normal_steps(cage, h_f, 'mesh_normal')
+    t0 = _clock(dev)
+    field, h_f, shape = density_grid(net, bbox_min, bbox_max, resolution, chunk)
+    t1 = _clock(dev)
+    v_np = verts.detach().cpu().numpy()
+    normals = vertex_normals(v_np, f_np).astype(np.float32)
+    tangents, creased = corner_tangents(v_np, f_np, normals, n)
+    t2 = time.perf_counter()
+    faces_d = torch.from_numpy(f_np).to(dev)
+    vn_d, tan_d, cr_d = torch.from_numpy(normals).to(dev), torch.from_numpy(tangents).to(dev), torch.from_numpy(creased.astype(np.uint8)).to(dev)
+    pts = ops.mesh_texel_points(verts.detach().contiguous(), faces_d, n)
+    t3 = _clock(dev)
+    atlas = torch.from_numpy(np.array(ops.MESH_NORMAL_FLAT, dtype=np.uint8)).to(dev).expand(H, W, 3).contiguous()
+    lo = np.asarray(bbox_min, dtype=np.float32).reshape(3).astype(np.float64)
+    level = float(np.float32(level))
+    _, offset, flags, normal = ops.mesh_normal_bake(verts.detach().contiguous(), vn_d, faces_d, tan_d, cr_d, pts, n, C, atlas, field,
+                                                    lo, h_f, level, S)
+    t4 = _clock(dev)
+    # how far the texels moved and how much the map adds: the angle between the field's normal and the search direction
+    m = n - 3
+    ij = torch.tensor([(i, j) for j in range(n - 1) for i in range(n - 1 - j)], device=dev, dtype=torch.float64)
+    b = torch.stack([m - ij[:, 0] - ij[:, 1], ij[:, 0], ij[:, 1]], -1)                    # [P,3]
+    nh = torch.einsum('pc,tck->tpk', b, vn_d.double()[faces_d.long()])
+    nh = nh / nh.norm(dim=-1, keepdim=True).clamp_min(1e-300)
+    nf = normal.double()
+    ang = torch.rad2deg(torch.atan2(torch.linalg.cross(nh, nf).norm(dim=-1), (nh * nf).sum(-1))).reshape(-1)
+    ang = ang[torch.isfinite(ang) & (flags.reshape(-1) & 3 == 0)]
+    off = offset.reshape(-1).abs().double()
+    off = off[torch.isfinite(off) & (flags.reshape(-1) & 1 == 0)]
+
+    def spread(x, scale=1.0):
+        if x.numel() == 0:
+            return {'mean': None, 'p99': None, 'max': None}
+        s = torch.sort(x).values
+        return {'mean': float(s.mean()) * scale, 'p99': float(s[min(s.numel() - 1, int(0.99 * s.numel()))]) * scale,
+                'max': float(s[-1]) * scale}
+    counts = {name: int((flags & bit != 0).sum().item()) for name, bit in ops.MESH_NORMAL_FLAGS.items()}
+    counts['none'] = int((flags == 0).sum().item())
+    stats = {'n': n, 'C': C, 'R': R, 'W': W, 'H': H, 'triangles': T, 'texels': T * P, 'resolution': int(resolution),
+             'grid_shape_xyz': list(shape), 'h_f': h_f, 'cage': float(cage), 'S': S, 'level': level,
+             'samples_per_texel': 2 * S + 7, 'texels_per_flag': counts, 'creased_triangles': int(creased.sum()),
+             'offset_m': spread(off), 'angle_to_search_direction_deg': spread(ang),
+             'bytes': {'grid': int(field.numel()) * 4, 'points': T * P * 12, 'tangents': T * 48, 'atlas': W * H * 3,
+                       'per_texel_outputs': T * P * 17},
+             'seconds': {'grid': round(t1 - t0, 4), 'tangents': round(t2 - t1, 4), 'points': round(t3 - t2, 4), 'bake': round(t4 - t3, 4)},
+             'tangents': tangents, 'creased': creased, 'normals': normals}
+    return atlas, offset, flags, stats
+
+
+def export_normal_map(net, out_dir, kept, bbox_min, bbox_max, level, mesh_resolution, cell, normal=None, chunk=1 << 21):
+    """<out_dir>/texture_normal.png and texture_normal.json of the kept mesh of export_mesh(keep=...) -> the sidecar's dict.
+    normal: the mesh_normal keys (NORMAL_DEFAULTS); cell: mesh_texture.cell, so that the map shares the colour atlas' layout and
+    TEXCOORD_0.  kept receives 'texture_normal': {'atlas': the device tensor, 'n', 'C', 'png': the bytes of the PNG file,
+    'tangents': float32 [T,3,4]}, what gltf.write_glb and mesh_view.export_views take."""
+    import io
+
+    from PIL import Image
+    normal = check_normal(NORMAL_DEFAULTS if normal is None else normal)
+    resolution = max(NORMAL_MIN_RESOLUTION, int(mesh_resolution)) if normal['resolution'] is None else normal['resolution']
+    cage = float(kept['h']) if normal['cage'] is None else normal['cage']
+    n = int(cell)
+    atlas, offset, flags, info = bake_normal_map(net, kept['verts'], kept['faces'], n, level, bbox_min, bbox_max, resolution, cage, chunk)
+    tangents = info.pop('tangents')
+    info.pop('creased'), info.pop('normals')
+    t0 = time.perf_counter()
+    blob = io.BytesIO()
+    Image.fromarray(atlas.cpu().numpy()).save(blob, format='PNG')
+    png = blob.getvalue()
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, 'texture_normal.png'), 'wb') as out:
+        out.write(png)
+    h = float(kept['h'])
+    info['offset_coarse_voxels'] = {k: (None if v is None else v / h) for k, v in info['offset_m'].items()}
+    info['bytes']['png'] = len(png)
+    info['seconds']['write'] = round(time.perf_counter() - t0, 4)
+    total = sum(info['seconds'].values())
+    info['share_of_seconds'] = {k: (round(v / total, 4) if total > 0 else None) for k, v in info['seconds'].items()}
+    kept['texture_normal'] = {'atlas': atlas, 'n': n, 'C': info['C'], 'png': png, 'tangents': tangents}
+    _write_sidecar(os.path.join(out_dir, 'texture_normal.json'), info)
+    return info
 
 
 # ------------------------------------------------------------------ the photographs on the atlas (DESIGN.md section 7p)

@@ -1867,6 +1867,116 @@ def mesh_resolve_textured(keys, faces, xy, z, atlas, n, C, bgcolor):
     return rgb
 
 
+# ------------------------------------------------------------------ the normal map of the exported mesh
+MESH_NORMAL_MAX_STEPS = 64
+MESH_NORMAL_FLAGS = {'no_crossing': 1, 'no_gradient': 2, 'flat': 4, 'face_direction': 8}
+MESH_NORMAL_FLAT = (128, 128, 255)
+
+
+def mesh_normal_steps(cage, h_f, who='mesh_normal_bake'):
+    """S = ceil(cage / (h_f / 2)), the steps of half a fine voxel to either side of a texel; S outside 1..64 is refused by name."""
+    cage, h_f = float(cage), float(h_f)
+    if not (0.0 < h_f < float('inf')) or not (0.0 < cage < float('inf')):
+        raise RuntimeError(f'{who}: cage = {cage!r} and h_f = {h_f!r} must be positive finite lengths')
+    S = int(math.ceil(cage / (h_f / 2.0)))
+    if not 1 <= S <= MESH_NORMAL_MAX_STEPS:
+        raise RuntimeError(f'{who}: cage = {cage!r} at a fine voxel of {h_f!r} takes S = {S} steps, outside 1..{MESH_NORMAL_MAX_STEPS} '
+                           '(lower mesh_normal.cage or mesh_normal.resolution)')
+    return S
+
+
+def mesh_normal_bake(verts, vnormals, faces, tangents, creased, pts, n, C, atlas, field, lo, h_f, level, S):
+    """The normal map's texels (occnerf_mesh_normal_bake): verts / vnormals float32 [V,3], faces int32 [T,3], tangents float32
+    [T,3,4] and creased uint8 [T] (mesh.corner_tangents), pts float32 [T,P,3] (mesh_texel_points), atlas uint8 [H,W,3] with
+    W = C n, filled by the caller with the flat code and written IN PLACE, field float32 [nz,ny,nx] with grid point (i,j,k) at
+    lo + (i,j,k) h_f (lo: 3 host values, float64), level the iso-value (float32), S the steps of h_f / 2 to either side
+    -> (atlas, offset float32 [T,P], flags uint8 [T,P], normal float32 [T,P,3]).  A face index outside [0, V) is refused by
+    name after one blocking read of the kernel's status word (the kernel itself never uses one as an address).  T = 0 launches
+    nothing."""
+    n = _mesh_texture_cell('mesh_normal_bake', n)
+    pv = _mesh_points('mesh_normal_bake: verts', verts)
+    pn = _mesh_points('mesh_normal_bake: vnormals', vnormals)
+    pf = _chk(faces, torch.int32, 'mesh_normal_bake: faces')
+    dev = verts.device
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != dev:
+        raise RuntimeError(f'mesh_normal_bake: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
+    V, T, P = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2
+    if V >= 1 << 31 or T * P >= 1 << 31:
+        raise RuntimeError(f'mesh_normal_bake: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
+    if tuple(vnormals.shape) != (V, 3) or vnormals.device != dev:
+        raise RuntimeError(f'mesh_normal_bake: vnormals must be float32 [{V},3] on the device of verts, got {tuple(vnormals.shape)}')
+    pt = _chk(tangents, torch.float32, 'mesh_normal_bake: tangents')
+    pc = _chk(creased, torch.uint8, 'mesh_normal_bake: creased')
+    pp = _chk(pts, torch.float32, 'mesh_normal_bake: pts')
+    if tuple(tangents.shape) != (T, 3, 4) or tuple(creased.shape) != (T,) or tuple(pts.shape) != (T, P, 3) or \
+            not (tangents.device == creased.device == pts.device == dev):
+        raise RuntimeError(f'mesh_normal_bake: tangents [{T},3,4], creased [{T}] and pts [{T},{P},3] must lie on the device of verts, '
+                           f'got {tuple(tangents.shape)}, {tuple(creased.shape)} and {tuple(pts.shape)}')
+    pa, H, W, C = _mesh_texture_atlas('mesh_normal_bake', atlas, T, n, C, dev)
+    pg, nx, ny, nz = _mesh_field('mesh_normal_bake', field)
+    if field.device != dev:
+        raise RuntimeError('mesh_normal_bake: field must lie on the device of verts')
+    lo = np.ascontiguousarray(np.asarray(lo, dtype=np.float64).reshape(3))
+    h_f, S = float(h_f), int(S)
+    if not (0.0 < h_f < float('inf')) or not np.all(np.isfinite(lo)):
+        raise RuntimeError(f'mesh_normal_bake: lo = {lo.tolist()} / h_f = {h_f!r}: a finite corner and a positive finite voxel edge are needed')
+    if not 1 <= S <= MESH_NORMAL_MAX_STEPS:
+        raise RuntimeError(f'mesh_normal_bake: S = {S} steps outside 1..{MESH_NORMAL_MAX_STEPS}')
+    offset = torch.empty(T, P, device=dev, dtype=torch.float32)
+    flags = torch.empty(T, P, device=dev, dtype=torch.uint8)
+    normal = torch.empty(T, P, 3, device=dev, dtype=torch.float32)
+    if T == 0:
+        return atlas, offset, flags, normal
+    status = torch.zeros(1, device=dev, dtype=torch.int32)
+    with _guard(verts):
+        rc = _lib.lib().occnerf_mesh_normal_bake(pv, pn, V, pf, T, pt, pc, pp, n, C, H, W, pg, nx, ny, nz, lo.ctypes.data, h_f,
+                                                 float(np.float32(level)), S, pa, offset.data_ptr(), flags.data_ptr(),
+                                                 normal.data_ptr(), status.data_ptr(), _stream(verts))
+    _lib.check(rc, 'mesh_normal_bake')
+    if int(status.item()) != 0:
+        raise RuntimeError(f'mesh_normal_bake: a face index lies outside [0, {V})')
+    return atlas, offset, flags, normal
+
+
+def mesh_ray_matrix(K, E):
+    """float64 3x3 M with M (column, row, 1) the ray direction of a pixel in the space E looks at: R^T K^-1 of K 3x3 and
+    E = [R | t] 4x4 on the host."""
+    K, E = _host_matrix64(K, (3, 3), 'mesh_ray_matrix: K'), _host_matrix64(E, (4, 4), 'mesh_ray_matrix: E')
+    return np.ascontiguousarray(E[:3, :3].T @ np.linalg.inv(K))
+
+
+def mesh_resolve_lit(keys, faces, xy, z, vnormals, tangents, atlas, n, C, M, bgcolor):
+    """Two headlight panels of mesh_raster's keys (occnerf_mesh_resolve_lit): keys int64 [H,W], faces int32 [T,3], mesh_project's
+    xy / z, vnormals float32 [V,3] and tangents float32 [T,3,4] of the posed mesh, the normal atlas uint8 [aH,aW,3] of cell edge
+    n with C cells per row, M 3x3 float64 on the host (mesh_ray_matrix), bgcolor 3 values 0..255 on the host
+    -> (shade_geometry, shade_mapped) uint8 [H,W,3]: the interpolated vertex normal alone, and the normal the atlas gives in
+    the frame a glTF viewer reconstructs.  No triangle: the background."""
+    n = _mesh_texture_cell('mesh_resolve_lit', n)
+    pk = _chk(keys, torch.int64, 'mesh_resolve_lit: keys')
+    if keys.dim() != 2:
+        raise RuntimeError(f'mesh_resolve_lit: keys must be int64 [H,W], got {tuple(keys.shape)}')
+    H, W = (int(s) for s in keys.shape)
+    pf, px, pz, _, T, V, H, W = _mesh_raster_args('mesh_resolve_lit', faces, xy, z, None, H, W)
+    dev = faces.device
+    if keys.device != dev:
+        raise RuntimeError('mesh_resolve_lit: keys must be mesh_raster\'s, on the device of faces')
+    pn = _mesh_points('mesh_resolve_lit: vnormals', vnormals)
+    pt = _chk(tangents, torch.float32, 'mesh_resolve_lit: tangents')
+    if tuple(vnormals.shape) != (V, 3) or tuple(tangents.shape) != (T, 3, 4) or vnormals.device != dev or tangents.device != dev:
+        raise RuntimeError(f'mesh_resolve_lit: vnormals [{V},3] and tangents [{T},3,4] must lie on the device of faces, got '
+                           f'{tuple(vnormals.shape)} and {tuple(tangents.shape)}')
+    pa, aH, aW, C = _mesh_texture_atlas('mesh_resolve_lit', atlas, T, n, C, dev)
+    M = _host_matrix64(M, (3, 3), 'mesh_resolve_lit: M')
+    bg = _mesh_bgcolor(bgcolor)
+    geometry = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    mapped = torch.empty(H, W, 3, device=dev, dtype=torch.uint8)
+    with _guard(faces):
+        rc = _lib.lib().occnerf_mesh_resolve_lit(pk, pf, T, V, px, pz, H, W, pn, pt, pa, aH, aW, n, C, M.ctypes.data,
+                                                 bg.ctypes.data, geometry.data_ptr(), mapped.data_ptr(), _stream(faces))
+    _lib.check(rc, 'mesh_resolve_lit')
+    return geometry, mapped
+
+
 # ------------------------------------------------------------------ the photographs on the atlas (DESIGN.md section 7p)
 def mesh_texture_project(xy, z, vflag, verts, pflag, faces, n, K, E, keys, photo, inside, bias, acc, seen):
     """One frame onto the atlas' accumulators (occnerf_mesh_texture_project): xy int32 [T P,2] / z float64 [T P] / vflag uint8

@@ -9,7 +9,8 @@ seeded random-init checkpoint (occnerf_amd/checkpoint.py) when no .tar is on dis
 with `mesh_view.frames` (a prepared dataset only) also mesh/view/<frame name>.png and mesh/view.json; with `mesh_rig.enable True`
 also mesh/rigged.glb, the mesh with a skeleton, skin weights and the motion of `mesh_rig.frames`, and mesh/rig.json; with
 `mesh_texture.enable True` also mesh/texture.png, the model's colour on a per-triangle atlas of the mesh; with
-`mesh_photo.enable True` also mesh/texture_photo.png, the dataset's photographs projected onto that atlas (run_mesh below).
+`mesh_photo.enable True` also mesh/texture_photo.png, the dataset's photographs projected onto that atlas; with
+`mesh_normal.enable True` also mesh/texture_normal.png, a tangent-space normal map of the density field (run_mesh below).
 `show_depth` / `show_normal` / `show_shaded True` append the geometry the renderer sees as panels behind [rgb, truth, alpha];
 `geometry.save True` writes its raw maps to <folder>_geometry/NNNNNN.npz beside geometry.json (occnerf_amd/gbuffer.py).
 `--type animate animate.motion PATH` drives the subject of a prepared dataset with a motion it has not seen (occnerf_amd/
@@ -295,6 +296,12 @@ def run_mesh():
     (occnerf_amd/mesh.py export_photo_texture) -> mesh/texture_photo.png (what the frames saw, the colour
     field elsewhere), texture_seen.png (how many frames saw each texel) and texture_photo.json; with mesh_photo.in_glb the
     glTF files carry that image, and every mesh_view panel gains a photo-textured render.
+    With mesh_normal.enable as well (it needs mesh_texture.enable), also a tangent-space normal map on that atlas (occnerf_amd/
+    mesh.py export_normal_map): a fine density grid of mesh_normal.resolution voxels is the detail source,
+    every texel is projected onto its surface, at most mesh_normal.cage metres away, and the field's normal there is stored in
+    the tangent frame of the glTF -> mesh/texture_normal.png and texture_normal.json; with mesh_normal.in_glb (it needs
+    mesh.normals) the glTF files carry TANGENT and the map as the material's normalTexture, and every mesh_view panel gains two
+    grey renders under a headlight, the geometry's normals beside the map's.
     Rank 0 alone works."""
     from occnerf_amd.mesh import MeshPoser, PoseFrames, export_mesh, export_posed
     ignore_non_rigid = bool(cfg.ignore_non_rigid_motions)
@@ -337,6 +344,15 @@ def run_mesh():
             if resolve_dataset_path(cfg, 'movement') is None:
                 raise SystemExit('mesh_photo.enable: the photographs and masks are those of a prepared dataset; the synthetic '
                                  'frame source has none (set train.dataset_path or movement.dataset)')
+        mnor = cfg.get('mesh_normal') or {}
+        mapping = bool(mnor.get('enable', False))
+        if mapping:
+            from occnerf_amd.mesh import check_normal
+            mnor = check_normal(mnor)
+            if not texturing:
+                raise SystemExit('mesh_normal.enable: the normal map lies on the atlas of mesh_texture.enable, which is not set')
+            if mnor['in_glb'] and not bool(m.normals):
+                raise SystemExit("mesh_normal.in_glb: glTF's TANGENT is read against NORMAL, and mesh.normals is False")
         kept = {} if posing or viewing or rigging or texturing else None
         info = export_mesh(model, out_dir, box[0], bbox_max, resolution=int(m.resolution), level=m.get('level'),
                            normals=bool(m.normals), chunk=int(m.chunk), keep=kept, components=m.get('components', 'all'),
@@ -353,6 +369,15 @@ def run_mesh():
             tex = export_texture(model, out_dir, kept, mtex, chunk=int(m.chunk))
             print(f"texture: {tex['texels_queried']} texels of {tex['triangles']} triangles in cells of {tex['n']} -> "
                   f"{os.path.join(out_dir, 'texture.png')} ({tex['W']} x {tex['H']}, {100.0 * tex['unowned_share']:.1f} % unowned)")
+            if mapping:
+                # the density field's normals on the same atlas
+                from occnerf_amd.mesh import export_normal_map, with_normal_map
+                nm = export_normal_map(model, out_dir, kept, box[0], bbox_max, kept['level'], int(m.resolution), mtex['cell'], mnor,
+                                       chunk=int(m.chunk))
+                print(f"normal map: {nm['texels']} texels against a {nm['grid_shape_xyz']} grid, {nm['texels_per_flag']['none']} "
+                      f"without a flag, {nm['creased_triangles']} creased triangles -> {os.path.join(out_dir, 'texture_normal.png')}")
+                if mnor['in_glb']:
+                    kept['texture'] = with_normal_map(kept['texture'], kept['texture_normal'])
             if not rigging and not photographing:
                 size = export_textured(out_dir, kept, normals=bool(m.normals))
                 print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
@@ -374,7 +399,11 @@ def run_mesh():
             ph = export_photo_texture(model, out_dir, kept, dataset, mph, poser=view_poser)
             print(f"photo texture: {len(ph['frames'])} frames, {100.0 * ph['seen_share']:.1f} % of {ph['owned_texels']} texels seen at "
                   f"least once (depth bias {ph['bias_m']:g} m) -> {os.path.join(out_dir, 'texture_photo.png')}")
-            glb_texture = kept['texture_photo'] if mph['in_glb'] else kept['texture']
+            glb_texture = kept['texture']             # (with mesh_normal.in_glb it carries the normal map already)
+            if mph['in_glb']:
+                glb_texture = kept['texture_photo']
+                if mapping and mnor['in_glb']:
+                    glb_texture = with_normal_map(glb_texture, kept['texture_normal'])
             if not rigging:
                 size = export_textured(out_dir, {**kept, 'texture': glb_texture}, normals=bool(m.normals))
                 print(f"texture: the static textured mesh -> {os.path.join(out_dir, 'textured.glb')} ({size} bytes)")
@@ -412,7 +441,8 @@ def run_mesh():
             views = export_views(model, out_dir, kept, dataset, mv.frames, panels=bool(mv.get('panels', True)), bgcolor=cfg.bgcolor,
                                  poser=view_poser,
                                  **({'texture': kept['texture']} if texturing else {}),
-                                 **({'photo': kept['texture_photo']} if photographing else {}))
+                                 **({'photo': kept['texture_photo']} if photographing else {}),
+                                 **({'normal': kept['texture_normal']} if mapping else {}))
             for f in views['frames']:
                 iou = 'none (empty union)' if f['iou'] is None else f"{f['iou']:.4f}"
                 print(f"view {f['name']}: IoU {iou} ({f['intersection']} / {f['union']} pixels), {f['covered']} pixels covered, "
