@@ -7,10 +7,10 @@
 //                       the level, six samples for the central difference there, the normal in the frame [T B n] by the cofactor
 //                       formula, three bytes at the texel's place in the atlas; the offset, the flags and the object-space normal
 //                       per texel beside it;
-//   mesh_resolve_lit    one thread per pixel of mesh_raster's keys: the winner's perspective-correct weights as
-//                       mesh_texture.hip's resolve forms them, the interpolated corner normal and tangent, the normal atlas
-//                       through section 7o's sampler (the blend kept unrounded), and two grey panels by section 7k's headlight
-//                       rule: the geometry's normal alone and the mapped one.
+//   mesh_resolve_lit    one thread per pixel of mesh_raster's keys: the winner's perspective-correct weights (mesh_screen.h),
+//                       the interpolated corner normal and tangent, the normal atlas through section 7o's sampler (mesh_atlas.h,
+//                       the blend kept unrounded), and two grey panels by section 7k's headlight rule: the geometry's normal
+//                       alone and the mapped one.
 //
 // fp64 on the float32 inputs with + - * / sqrt floor rint and comparisons only, one rounding per operator in the order of
 // tests/mesh_normal_restatement.py (the tree is built with -ffp-contract=off).  No atomics, no LDS; every output is a pure function
@@ -44,7 +44,6 @@ struct NormalGrid {
 
 __device__ __forceinline__ bool usable(double l2) { return l2 > 0.0 && l2 <= kFiniteMax; }          // (a NaN fails)
 __device__ __forceinline__ bool finite64(double x) { return fabs(x) <= kFiniteMax; }                // (a NaN fails)
-__device__ __forceinline__ double dot3(const double a[3], const double b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
 __device__ __forceinline__ void cross3(const double a[3], const double b[3], double c[3]) {
     c[0] = a[1] * b[2] - a[2] * b[1];
     c[1] = a[2] * b[0] - a[0] * b[2];
@@ -100,10 +99,8 @@ __global__ __launch_bounds__(kTexThreads) void mesh_normal_bake_kernel(
     uint8_t *__restrict__ flags, float *__restrict__ normal, int32_t *__restrict__ status) {
     const int64_t g = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (g >= T * P) return;
-    const int64_t t = g / P;
     int i, j, ax, ay;
-    texel_of((int)(g - t * P), n, i, j);
-    atlas_of(t, i, j, n, C, ax, ay);
+    const int64_t t = texel_walk(g, n, P, C, i, j, ax, ay);
     uint8_t *out = atlas + ((int64_t)ay * W + ax) * 3;
     const int32_t v0 = faces[t * 3], v1 = faces[t * 3 + 1], v2 = faces[t * 3 + 2];
     if (v0 < 0 || v0 >= V || v1 < 0 || v1 >= V || v2 < 0 || v2 >= V) {
@@ -212,82 +209,40 @@ __global__ __launch_bounds__(kTexThreads) void mesh_resolve_lit_kernel(
     const int64_t pix = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (pix >= (int64_t)H * W) return;
     uint8_t geo[3] = {bg.c[0], bg.c[1], bg.c[2]}, map[3] = {bg.c[0], bg.c[1], bg.c[2]};
-    const unsigned long long key = keys[pix];
-    const int64_t t = (int64_t)(key & 0xFFFFFFFFull);
-    if (key != kRasterEmpty && t < T) {
-        const int32_t v0 = faces[t * 3], v1 = faces[t * 3 + 1], v2 = faces[t * 3 + 2];
-        if (v0 >= 0 && v0 < V && v1 >= 0 && v1 < V && v2 >= 0 && v2 < V) {
-            const int64_t X0 = xy[(int64_t)v0 * 2], Y0 = xy[(int64_t)v0 * 2 + 1];
-            const int64_t X1 = xy[(int64_t)v1 * 2], Y1 = xy[(int64_t)v1 * 2 + 1];
-            const int64_t X2 = xy[(int64_t)v2 * 2], Y2 = xy[(int64_t)v2 * 2 + 1];
-            const double z0 = z[v0], z1 = z[v1], z2 = z[v2];
-            const int64_t As = (X1 - X0) * (Y2 - Y0) - (Y1 - Y0) * (X2 - X0);
-            if (As != 0 && z0 > 0.0 && z1 > 0.0 && z2 > 0.0) {           // (a flagged vertex has z = 0)
-                // the screen triangle and the weights exactly as mesh_texture.hip's mesh_resolve_textured_kernel states them
-                const bool flip = As < 0;
-                const int64_t col = pix % W, row = pix / W;
-                const int64_t px = 256ll * col, py = 256ll * row;
-                const int64_t Xa = X0, Ya = Y0;
-                const int64_t Xb = flip ? X2 : X1, Yb = flip ? Y2 : Y1, Xc = flip ? X1 : X2, Yc = flip ? Y1 : Y2;
-                const double zb = flip ? z2 : z1, zc = flip ? z1 : z2;
-                const int64_t e0 = (Xc - Xb) * (py - Yb) - (Yc - Yb) * (px - Xb);
-                const int64_t e1 = (Xa - Xc) * (py - Yc) - (Ya - Yc) * (px - Xc);
-                const int64_t e2 = (Xb - Xa) * (py - Ya) - (Yb - Ya) * (px - Xa);
-                const double a = (double)(flip ? -As : As);
-                const double q0 = ((double)e0 / a) / z0, q1 = ((double)e1 / a) / zb, q2 = ((double)e2 / a) / zc;
-                const double iz = (q0 + q1) + q2;
-                const double w0 = q0 / iz, wb = q1 / iz, wc = q2 / iz;
-                const double w1 = flip ? wc : wb, w2 = flip ? wb : wc;   // back in the face's own order
-                // the interpolated corner normal and tangent
-                double N0[3], N1[3], N2[3], Nh[3], T0[3], T1[3], T2[3], Th[3], B[3], d[3];
-                load3(vnormals + (int64_t)v0 * 3, N0), load3(vnormals + (int64_t)v1 * 3, N1), load3(vnormals + (int64_t)v2 * 3, N2);
-                load3(tangents + (t * 3) * 4, T0), load3(tangents + (t * 3 + 1) * 4, T1), load3(tangents + (t * 3 + 2) * 4, T2);
-                blend3(w0, w1, w2, N0, N1, N2, Nh);
-                blend3(w0, w1, w2, T0, T1, T2, Th);
-                const bool okN = normalise3(Nh), okT = normalise3(Th);
-                const double dc = (double)col, dr = (double)row;
+    ScreenWinner win;
+    if (screen_winner(keys[pix], faces, T, V, xy, z, pix, W, win)) {
+        const int64_t t = win.t;
+        // the interpolated corner normal and tangent
+        double N0[3], N1[3], N2[3], Nh[3], T0[3], T1[3], T2[3], Th[3], B[3], d[3];
+        load3(vnormals + (int64_t)win.v0 * 3, N0), load3(vnormals + (int64_t)win.v1 * 3, N1), load3(vnormals + (int64_t)win.v2 * 3, N2);
+        load3(tangents + (t * 3) * 4, T0), load3(tangents + (t * 3 + 1) * 4, T1), load3(tangents + (t * 3 + 2) * 4, T2);
+        blend3(win.w0, win.w1, win.w2, N0, N1, N2, Nh);
+        blend3(win.w0, win.w1, win.w2, T0, T1, T2, Th);
+        const bool okN = normalise3(Nh), okT = normalise3(Th);
+        const double dc = (double)win.col, dr = (double)win.row;
 #pragma unroll
-                for (int k = 0; k < 3; k++) d[k] = (cam.M[k * 3] * dc + cam.M[k * 3 + 1] * dr) + cam.M[k * 3 + 2];
-                const double nanv[3] = {__longlong_as_double(0x7FF8000000000000ll), 0.0, 0.0};
-                geo[0] = geo[1] = geo[2] = headlight(okN ? Nh : nanv, d);
-                // the normal atlas through section 7o's sampler, the blend kept unrounded
-                const double dm = (double)(n - 3);
-                const double xr = w1 * dm, yr = w2 * dm;
-                const double x = xr > 0.0 ? (xr < dm ? xr : dm) : 0.0;
-                const double ym = dm - x;
-                const double y = yr > 0.0 ? (yr < ym ? yr : ym) : 0.0;
-                const double fx = floor(x), fy = floor(y);
-                const double fax = x - fx, fay = y - fy;
-                const int i0 = (int)fx, j0 = (int)fy;
-                const int i1 = i0 + 1 < n ? i0 + 1 : n - 1, j1 = j0 + 1 < n ? j0 + 1 : n - 1;      // (0 <= i0, j0 <= n - 3)
-                const double w00 = (1.0 - fax) * (1.0 - fay), w10 = fax * (1.0 - fay), w01 = (1.0 - fax) * fay, w11 = fax * fay;
-                int x00, y00, x10, y10, x01, y01, x11, y11;
-                atlas_of(t, i0, j0, n, C, x00, y00);
-                atlas_of(t, i1, j0, n, C, x10, y10);
-                atlas_of(t, i0, j1, n, C, x01, y01);
-                atlas_of(t, i1, j1, n, C, x11, y11);
-                const uint8_t *c00 = atlas + ((int64_t)y00 * aW + x00) * 3, *c10 = atlas + ((int64_t)y10 * aW + x10) * 3;
-                const uint8_t *c01 = atlas + ((int64_t)y01 * aW + x01) * 3, *c11 = atlas + ((int64_t)y11 * aW + x11) * 3;
-                double c[3];
-                bool flat = true;                 // four taps of the flat code (128, 128, 255): the geometry's normal itself
+        for (int k = 0; k < 3; k++) d[k] = (cam.M[k * 3] * dc + cam.M[k * 3 + 1] * dr) + cam.M[k * 3 + 2];
+        const double nanv[3] = {__longlong_as_double(0x7FF8000000000000ll), 0.0, 0.0};
+        geo[0] = geo[1] = geo[2] = headlight(okN ? Nh : nanv, d);
+        // the normal atlas through section 7o's sampler, the blend kept unrounded
+        const AtlasTaps taps = atlas_taps(atlas, aW, t, win.w1, win.w2, n, C);
+        double c[3];
+        bool flat = true;                 // four taps of the flat code (128, 128, 255): the geometry's normal itself
 #pragma unroll
-                for (int k = 0; k < 3; k++) {
-                    const uint8_t code = k == 2 ? 255 : 128;
-                    flat = flat && c00[k] == code && c10[k] == code && c01[k] == code && c11[k] == code;
-                    const double s = ((w00 * (double)c00[k] + w10 * (double)c10[k]) + w01 * (double)c01[k]) + w11 * (double)c11[k];
-                    c[k] = s / 127.5 - 1.0;
-                }
-                if (flat) {
-                    map[0] = map[1] = map[2] = geo[0];
-                } else {
-                    double m[3];
-                    cross3(Nh, Th, B);
+        for (int k = 0; k < 3; k++) {
+            const uint8_t code = k == 2 ? 255 : 128;
+            flat = flat && taps.c00[k] == code && taps.c10[k] == code && taps.c01[k] == code && taps.c11[k] == code;
+            c[k] = taps.blend(k) / 127.5 - 1.0;
+        }
+        if (flat) {
+            map[0] = map[1] = map[2] = geo[0];
+        } else {
+            double m[3];
+            cross3(Nh, Th, B);
 #pragma unroll
-                    for (int k = 0; k < 3; k++) m[k] = (c[0] * Th[k] + c[1] * B[k]) + c[2] * Nh[k];
-                    const bool okM = okN && okT && normalise3(m);
-                    map[0] = map[1] = map[2] = headlight(okM ? m : nanv, d);
-                }
-            }
+            for (int k = 0; k < 3; k++) m[k] = (c[0] * Th[k] + c[1] * B[k]) + c[2] * Nh[k];
+            const bool okM = okN && okT && normalise3(m);
+            map[0] = map[1] = map[2] = headlight(okM ? m : nanv, d);
         }
     }
 #pragma unroll
@@ -302,13 +257,10 @@ OCC_API int occnerf_mesh_normal_bake(const float *verts, const float *vnormals, 
                                      const double *h_lo, double h_f, float level, int32_t S, uint8_t *atlas, float *offset,
                                      uint8_t *flags, float *normal, int32_t *status, void *stream) {
     using namespace occ;
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_normal_bake: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
-    const int64_t P = (int64_t)n * (n - 1) / 2;
+    if (!tex_cell_ok("mesh_normal_bake", n)) return 1;
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_normal_bake: V=%lld outside 0..2^31-1", (long long)V);
-    OCC_REQUIRE(T >= 0 && T < (1ll << 31) && T * P < (1ll << 31), "mesh_normal_bake: T=%lld with %lld texels each reaches 2^31",
-                (long long)T, (long long)P);
-    OCC_REQUIRE(tex_layout_ok(T, n, C, H, W), "mesh_normal_bake: an atlas of H=%d W=%d with C=%d cells of %d per row does not hold "
-                "T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", H, W, C, n, (long long)T, kTexMaxSide);
+    int64_t P;
+    if (!tex_count_ok("mesh_normal_bake", T, n, P) || !tex_atlas_ok("mesh_normal_bake", T, n, C, H, W)) return 1;
     OCC_REQUIRE(nx >= 2 && ny >= 2 && nz >= 2 && (int64_t)nx * ny * nz < (1ll << 31),
                 "mesh_normal_bake: a grid of %d x %d x %d points: every axis needs two, all of them fewer than 2^31", nx, ny, nz);
     OCC_REQUIRE(S >= 1 && S <= kNormalMaxSteps, "mesh_normal_bake: S=%d steps outside 1..%d", S, kNormalMaxSteps);
@@ -334,13 +286,12 @@ OCC_API int occnerf_mesh_resolve_lit(const uint64_t *keys, const int32_t *faces,
     using namespace occ;
     OCC_REQUIRE(h_bgcolor && h_M, "mesh_resolve_lit: null argument");
     OCC_REQUIRE(raster_size_ok(Himg, Wimg), "mesh_resolve_lit: H=%d W=%d outside 1..16384 or more than 2^28 pixels", Himg, Wimg);
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_resolve_lit: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
+    if (!tex_cell_ok("mesh_resolve_lit", n)) return 1;
     OCC_REQUIRE(T >= 0 && T < (1ll << 31), "mesh_resolve_lit: T=%lld outside 0..2^31-1", (long long)T);
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_resolve_lit: V=%lld outside 0..2^31-1", (long long)V);
     OCC_REQUIRE(keys && shade_geometry && shade_mapped, "mesh_resolve_lit: null argument");
     if (T > 0 && V > 0) {
-        OCC_REQUIRE(tex_layout_ok(T, n, C, aH, aW), "mesh_resolve_lit: an atlas of H=%d W=%d with C=%d cells of %d per row does "
-                    "not hold T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", aH, aW, C, n, (long long)T, kTexMaxSide);
+        if (!tex_atlas_ok("mesh_resolve_lit", T, n, C, aH, aW)) return 1;
         OCC_REQUIRE(faces && xy && z && vnormals && tangents && atlas, "mesh_resolve_lit: null argument");
     }
     LitCamera cam;

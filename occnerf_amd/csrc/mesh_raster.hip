@@ -17,8 +17,9 @@
 //
 // Coverage is int64 arithmetic on the fixed-point coordinates; the fp64 steps use + * / rint and comparisons only, one rounding
 // per operator in the order of tests/mesh_raster_restatement.py (the tree is built with -ffp-contract=off): the outputs are that
-// file's, bit for bit.  Every index read from faces or from a key is checked before it is used as an address.  The empty key, the
-// image-size test, the background and the byte store are mesh_screen.h's, shared with mesh_texture.hip's textured resolve.
+// file's, bit for bit.  Every index read from faces or from a key is checked before it is used as an address.  The camera with
+// its vertex rule and three limits, the empty key, the image-size test, the background and the byte store are mesh_screen.h's,
+// shared with mesh_texture.hip and mesh_normal.hip.
 #include "common.h"
 #include "mesh_screen.h"
 
@@ -27,32 +28,17 @@ namespace occ {
 constexpr int kRasterThreads = 256;
 constexpr int kRasterWide = 64;                   // samples in the clipped box above which a triangle goes to the wide pass
 constexpr int kRasterWideBlocks = 1024;           // of kRasterThreads: 4096 waves stride over the list
-constexpr double kRasterNear = 1e-3;
-constexpr double kRasterFar = 1048576.0;          // 2^20
-constexpr double kRasterGuard = 4194304.0;        // 2^22 fixed-point units
 constexpr int kRasterMaxSide = 16384;
 constexpr int64_t kRasterMaxPixels = 1ll << 28;
 enum RasterCount : int { kCntIndex = 0, kCntNear, kCntGuard, kCntArea, kCntOffscreen, kCntWide, kCntCovered, kCntTotal };
 
-struct RasterCamera {
-    double fx, fy, cx, cy;
-    double R[9], t[3];
-};
-
-__global__ __launch_bounds__(kRasterThreads) void mesh_project_kernel(const float *__restrict__ pos, int64_t V, RasterCamera cam,
+__global__ __launch_bounds__(kRasterThreads) void mesh_project_kernel(const float *__restrict__ pos, int64_t V, ScreenCamera cam,
                                                                       int32_t *__restrict__ xy, double *__restrict__ z,
                                                                       uint8_t *__restrict__ vflag) {
     const int64_t i = (int64_t)blockIdx.x * kRasterThreads + threadIdx.x;
     if (i >= V) return;
-    const double p0 = (double)pos[i * 3], p1 = (double)pos[i * 3 + 1], p2 = (double)pos[i * 3 + 2];
-    double c[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) c[k] = ((cam.R[k * 3] * p0 + cam.R[k * 3 + 1] * p1) + cam.R[k * 3 + 2] * p2) + cam.t[k];
-    const double a = 256.0 * (cam.fx * (c[0] / c[2]) + cam.cx);
-    const double b = 256.0 * (cam.fy * (c[1] / c[2]) + cam.cy);
-    int flag = 0;
-    if (!(c[2] >= kRasterNear)) flag = 1;
-    else if (!(fabs(a) <= kRasterGuard && fabs(b) <= kRasterGuard && c[2] <= kRasterFar)) flag = 2;
+    double c[3], a, b;
+    const int flag = screen_vertex(cam, pos + i * 3, c, a, b);
     xy[i * 2] = flag ? 0 : (int32_t)rint(a);
     xy[i * 2 + 1] = flag ? 0 : (int32_t)rint(b);
     z[i] = flag ? 0.0 : c[2];
@@ -242,14 +228,8 @@ OCC_API int occnerf_mesh_project(const float *pos, int64_t V, const double *h_K,
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_project: V=%lld outside 0..2^31-1", (long long)V);
     if (V == 0) return 0;
     OCC_REQUIRE(pos && xy && z && vflag, "mesh_project: null pos / output with V=%lld", (long long)V);
-    RasterCamera cam;
-    cam.fx = h_K[0], cam.fy = h_K[4], cam.cx = h_K[2], cam.cy = h_K[5];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) cam.R[r * 3 + c] = h_E[r * 4 + c];
-        cam.t[r] = h_E[r * 4 + 3];
-    }
     hipLaunchKernelGGL(mesh_project_kernel, dim3((unsigned)((V + kRasterThreads - 1) / kRasterThreads)), dim3(kRasterThreads), 0,
-                       as_stream(stream), pos, V, cam, xy, z, vflag);
+                       as_stream(stream), pos, V, screen_camera(h_K, h_E), xy, z, vflag);
     return check_launch("mesh_project");
 }
 

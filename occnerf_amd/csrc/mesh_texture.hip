@@ -5,8 +5,8 @@
 //
 //   mesh_texel_points       one thread per texel: its canonical point, the colour field's query;
 //   mesh_texture_fill       one thread per texel: the queried colour as a byte at its place in the atlas;
-//   mesh_resolve_textured   one thread per pixel of mesh_raster's keys: the winner's perspective-correct weights as
-//                           mesh_raster.hip's resolve forms them, then four taps of the atlas, all of them the winner's own texels.
+//   mesh_resolve_textured   one thread per pixel of mesh_raster's keys: the winner's perspective-correct weights
+//                           (mesh_screen.h), then four taps of the atlas (mesh_atlas.h), all of them the winner's own texels.
 //   mesh_texture_project    the photographs on the atlas, one frame per call: one thread per triangle for
 //                           its weight in this frame, then one thread per texel: seen or not, four taps of the photograph in
 //                           integers, its own row of the int64 accumulators;
@@ -16,8 +16,9 @@
 // tests/mesh_texture_restatement.py (the tree is built with -ffp-contract=off); the fill's product is the float32 one of
 // image.to_8b_image.  No atomics; every output is a pure function of the inputs: the same bytes on every run.  Every index read
 // from faces or from a key is checked before it is used as an address, and every atlas address lies inside the C x R cells the
-// entry has checked against the atlas' size.  The empty key, the image-size test, the background and the byte store are
-// mesh_screen.h's, shared with mesh_raster.hip's resolve.
+// entry has checked against the atlas' size.  The camera and the vertex rule's three limits, dot3, the winner of a pixel, the
+// background and the byte store are mesh_screen.h's; the texel walk, the sampler and the entries' refusals on n, T P and the
+// atlas' shape are mesh_atlas.h's.
 #include "common.h"
 #include "mesh_atlas.h"
 #include "mesh_screen.h"
@@ -53,10 +54,8 @@ __global__ __launch_bounds__(kTexThreads) void mesh_texture_fill_kernel(const fl
                                                                         int W, uint8_t *__restrict__ atlas) {
     const int64_t g = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (g >= T * P) return;
-    const int64_t t = g / P;
     int i, j, x, y;
-    texel_of((int)(g - t * P), n, i, j);
-    atlas_of(t, i, j, n, C, x, y);
+    texel_walk(g, n, P, C, i, j, x, y);
     uint8_t *out = atlas + ((int64_t)y * W + x) * 3;
 #pragma unroll
     for (int c = 0; c < 3; c++) {
@@ -73,92 +72,35 @@ __global__ __launch_bounds__(kTexThreads) void mesh_resolve_textured_kernel(
     const int64_t pix = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (pix >= (int64_t)H * W) return;
     uint8_t out[3] = {bg.c[0], bg.c[1], bg.c[2]};
-    const unsigned long long key = keys[pix];
-    const int64_t t = (int64_t)(key & 0xFFFFFFFFull);
-    if (key != kRasterEmpty && t < T) {
-        const int32_t v0 = faces[t * 3], v1 = faces[t * 3 + 1], v2 = faces[t * 3 + 2];
-        if (v0 >= 0 && v0 < V && v1 >= 0 && v1 < V && v2 >= 0 && v2 < V) {
-            const int64_t X0 = xy[(int64_t)v0 * 2], Y0 = xy[(int64_t)v0 * 2 + 1];
-            const int64_t X1 = xy[(int64_t)v1 * 2], Y1 = xy[(int64_t)v1 * 2 + 1];
-            const int64_t X2 = xy[(int64_t)v2 * 2], Y2 = xy[(int64_t)v2 * 2 + 1];
-            const double z0 = z[v0], z1 = z[v1], z2 = z[v2];
-            const int64_t As = (X1 - X0) * (Y2 - Y0) - (Y1 - Y0) * (X2 - X0);
-            if (As != 0 && z0 > 0.0 && z1 > 0.0 && z2 > 0.0) {           // (a flagged vertex has z = 0)
-                // (a, b, c): the triangle as mesh_raster.hip's raster_setup orders it, vertices 1 and 2 exchanged when the area
-                // is negative; e_k, q_k and the weights are that triangle's, as resolve forms them
-                const bool flip = As < 0;
-                const int64_t px = 256ll * (pix % W), py = 256ll * (pix / W);
-                const int64_t Xa = X0, Ya = Y0;
-                const int64_t Xb = flip ? X2 : X1, Yb = flip ? Y2 : Y1, Xc = flip ? X1 : X2, Yc = flip ? Y1 : Y2;
-                const double zb = flip ? z2 : z1, zc = flip ? z1 : z2;
-                const int64_t e0 = (Xc - Xb) * (py - Yb) - (Yc - Yb) * (px - Xb);
-                const int64_t e1 = (Xa - Xc) * (py - Yc) - (Ya - Yc) * (px - Xc);
-                const int64_t e2 = (Xb - Xa) * (py - Ya) - (Yb - Ya) * (px - Xa);
-                const double a = (double)(flip ? -As : As);
-                const double q0 = ((double)e0 / a) / z0, q1 = ((double)e1 / a) / zb, q2 = ((double)e2 / a) / zc;
-                const double iz = (q0 + q1) + q2;
-                const double wb = q1 / iz, wc = q2 / iz;
-                const double w1 = flip ? wc : wb, w2 = flip ? wb : wc;   // back in the face's own order
-                const double dm = (double)(n - 3);
-                const double xr = w1 * dm, yr = w2 * dm;
-                const double x = xr > 0.0 ? (xr < dm ? xr : dm) : 0.0;
-                const double ym = dm - x;
-                const double y = yr > 0.0 ? (yr < ym ? yr : ym) : 0.0;
-                const double fx = floor(x), fy = floor(y);
-                const double ax = x - fx, ay = y - fy;
-                const int i0 = (int)fx, j0 = (int)fy;
-                const int i1 = i0 + 1 < n ? i0 + 1 : n - 1, j1 = j0 + 1 < n ? j0 + 1 : n - 1;      // (0 <= i0, j0 <= n - 3)
-                const double w00 = (1.0 - ax) * (1.0 - ay), w10 = ax * (1.0 - ay), w01 = (1.0 - ax) * ay, w11 = ax * ay;
-                int x00, y00, x10, y10, x01, y01, x11, y11;
-                atlas_of(t, i0, j0, n, C, x00, y00);
-                atlas_of(t, i1, j0, n, C, x10, y10);
-                atlas_of(t, i0, j1, n, C, x01, y01);
-                atlas_of(t, i1, j1, n, C, x11, y11);
-                const uint8_t *c00 = atlas + ((int64_t)y00 * aW + x00) * 3, *c10 = atlas + ((int64_t)y10 * aW + x10) * 3;
-                const uint8_t *c01 = atlas + ((int64_t)y01 * aW + x01) * 3, *c11 = atlas + ((int64_t)y11 * aW + x11) * 3;
+    ScreenWinner win;
+    if (screen_winner(keys[pix], faces, T, V, xy, z, pix, W, win)) {
+        const AtlasTaps taps = atlas_taps(atlas, aW, win.t, win.w1, win.w2, n, C);
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const double s = ((w00 * (double)c00[c] + w10 * (double)c10[c]) + w01 * (double)c01[c]) + w11 * (double)c11[c];
-                    out[c] = raster_byte(s);
-                }
-            }
-        }
+        for (int c = 0; c < 3; c++) out[c] = raster_byte(taps.blend(c));
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) rgb[pix * 3 + c] = out[c];
 }
 
 // ---------------------------------------------------------------- the photographs on the atlas
-// The camera and the limits of mesh_raster.hip's vertex rule, which the triangle weights apply to the posed
-// vertices; tests/test_mesh_photo_restatement.py holds the three numbers to the definition's.
-constexpr double kPhotoNear = 1e-3;
-constexpr double kPhotoFar = 1048576.0;           // 2^20
-constexpr double kPhotoGuard = 4194304.0;         // 2^22 fixed-point units
-
-struct PhotoCamera {
-    double fx, fy, cx, cy;
-    double R[9], t[3];
-};
-
-// The weight of a triangle in one frame: 1 .. 256, 0 (unusable: flagged, degenerate, grazing) or -1 (it faces away).
-__device__ __forceinline__ int photo_vertex(const PhotoCamera &cam, const float *__restrict__ p, double c[3]) {
+// The vertex rule of mesh_screen.h's screen_vertex, stated again without the coordinates it hands back: calling screen_vertex
+// here compiled the weights to other code, which ran outside the parent's range in two of six traced runs (DESIGN.md section
+// 7o).  The camera and the three limits are the header's.
+__device__ __forceinline__ int photo_vertex(const ScreenCamera &cam, const float *__restrict__ p, double c[3]) {
     const double p0 = (double)p[0], p1 = (double)p[1], p2 = (double)p[2];
 #pragma unroll
     for (int k = 0; k < 3; k++) c[k] = ((cam.R[k * 3] * p0 + cam.R[k * 3 + 1] * p1) + cam.R[k * 3 + 2] * p2) + cam.t[k];
     const double a = 256.0 * (cam.fx * (c[0] / c[2]) + cam.cx);
     const double b = 256.0 * (cam.fy * (c[1] / c[2]) + cam.cy);
-    if (!(c[2] >= kPhotoNear)) return 1;
-    if (!(fabs(a) <= kPhotoGuard && fabs(b) <= kPhotoGuard && c[2] <= kPhotoFar)) return 2;
+    if (!(c[2] >= kScreenNear)) return 1;
+    if (!(fabs(a) <= kScreenGuard && fabs(b) <= kScreenGuard && c[2] <= kScreenFar)) return 2;
     return 0;
 }
 
-__device__ __forceinline__ double photo_dot(const double a[3], const double b[3]) {
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2];
-}
-
+// The weight of a triangle in one frame: 1 .. 256, 0 (unusable: flagged, degenerate, grazing) or -1 (it faces away).
 __global__ __launch_bounds__(kTexThreads) void mesh_photo_weight_kernel(const float *__restrict__ verts,
                                                                         const uint8_t *__restrict__ pflag, int64_t V,
-                                                                        const int32_t *__restrict__ faces, int64_t T, PhotoCamera cam,
+                                                                        const int32_t *__restrict__ faces, int64_t T, ScreenCamera cam,
                                                                         int32_t *__restrict__ tw, int32_t *__restrict__ status) {
     const int64_t t = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (t >= T) return;
@@ -181,7 +123,7 @@ __global__ __launch_bounds__(kTexThreads) void mesh_photo_weight_kernel(const fl
         N[0] = e1[1] * e2[2] - e1[2] * e2[1];
         N[1] = e1[2] * e2[0] - e1[0] * e2[2];
         N[2] = e1[0] * e2[1] - e1[1] * e2[0];
-        const double d = photo_dot(N, g), NN = photo_dot(N, N), gg = photo_dot(g, g);
+        const double d = dot3(N, g), NN = dot3(N, N), gg = dot3(g, g);
         const double q = NN * gg;
         const double r = 256.0 * ((d * d) / q);
         if (q > 0.0 && q <= 1.7976931348623157e308 && r >= 0.0 && r <= 1.7976931348623157e308) {        // (a NaN fails)
@@ -241,10 +183,8 @@ __global__ __launch_bounds__(kTexThreads) void mesh_texture_blend_kernel(const l
                                                                          uint8_t *__restrict__ seen_img) {
     const int64_t g = (int64_t)blockIdx.x * kTexThreads + threadIdx.x;
     if (g >= T * P) return;
-    const int64_t t = g / P;
     int i, j, x, y;
-    texel_of((int)(g - t * P), n, i, j);
-    atlas_of(t, i, j, n, C, x, y);
+    texel_walk(g, n, P, C, i, j, x, y);
     const int64_t at = (int64_t)y * W + x;
     const int32_t s = seen[g];
     seen_img[at] = (uint8_t)(s < 0 ? 0 : (s < 255 ? s : 255));
@@ -264,11 +204,10 @@ __global__ __launch_bounds__(kTexThreads) void mesh_texture_blend_kernel(const l
 OCC_API int occnerf_mesh_texel_points(const float *verts, int64_t V, const int32_t *faces, int64_t T, int32_t n, float *pts,
                                       int32_t *status, void *stream) {
     using namespace occ;
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_texel_points: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
-    const int64_t P = (int64_t)n * (n - 1) / 2;
+    if (!tex_cell_ok("mesh_texel_points", n)) return 1;
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_texel_points: V=%lld outside 0..2^31-1", (long long)V);
-    OCC_REQUIRE(T >= 0 && T < (1ll << 31) && T * P < (1ll << 31), "mesh_texel_points: T=%lld with %lld texels each reaches 2^31",
-                (long long)T, (long long)P);
+    int64_t P;
+    if (!tex_count_ok("mesh_texel_points", T, n, P)) return 1;
     if (T == 0) return 0;
     OCC_REQUIRE(faces && pts && status && (verts || V == 0), "mesh_texel_points: null argument");
     const int64_t N = T * P;
@@ -280,12 +219,9 @@ OCC_API int occnerf_mesh_texel_points(const float *verts, int64_t V, const int32
 OCC_API int occnerf_mesh_texture_fill(const float *rgb, int64_t T, int32_t n, int32_t C, int32_t H, int32_t W, uint8_t *atlas,
                                       void *stream) {
     using namespace occ;
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_texture_fill: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
-    const int64_t P = (int64_t)n * (n - 1) / 2;
-    OCC_REQUIRE(T >= 0 && T < (1ll << 31) && T * P < (1ll << 31), "mesh_texture_fill: T=%lld with %lld texels each reaches 2^31",
-                (long long)T, (long long)P);
-    OCC_REQUIRE(tex_layout_ok(T, n, C, H, W), "mesh_texture_fill: an atlas of H=%d W=%d with C=%d cells of %d per row does not hold "
-                "T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", H, W, C, n, (long long)T, kTexMaxSide);
+    if (!tex_cell_ok("mesh_texture_fill", n)) return 1;
+    int64_t P;
+    if (!tex_count_ok("mesh_texture_fill", T, n, P) || !tex_atlas_ok("mesh_texture_fill", T, n, C, H, W)) return 1;
     if (T == 0) return 0;
     OCC_REQUIRE(rgb && atlas, "mesh_texture_fill: null argument");
     const int64_t N = T * P;
@@ -301,13 +237,12 @@ OCC_API int occnerf_mesh_resolve_textured(const uint64_t *keys, const int32_t *f
     OCC_REQUIRE(h_bgcolor, "mesh_resolve_textured: null argument");
     OCC_REQUIRE(raster_size_ok(Himg, Wimg),
                 "mesh_resolve_textured: H=%d W=%d outside 1..16384 or more than 2^28 pixels", Himg, Wimg);
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_resolve_textured: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
+    if (!tex_cell_ok("mesh_resolve_textured", n)) return 1;
     OCC_REQUIRE(T >= 0 && T < (1ll << 31), "mesh_resolve_textured: T=%lld outside 0..2^31-1", (long long)T);
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_resolve_textured: V=%lld outside 0..2^31-1", (long long)V);
     OCC_REQUIRE(keys && rgb, "mesh_resolve_textured: null argument");
     if (T > 0 && V > 0) {
-        OCC_REQUIRE(tex_layout_ok(T, n, C, aH, aW), "mesh_resolve_textured: an atlas of H=%d W=%d with C=%d cells of %d per row does "
-                    "not hold T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", aH, aW, C, n, (long long)T, kTexMaxSide);
+        if (!tex_atlas_ok("mesh_resolve_textured", T, n, C, aH, aW)) return 1;
         OCC_REQUIRE(faces && xy && z && atlas, "mesh_resolve_textured: null argument");
     }
     RasterBg bg;
@@ -328,25 +263,18 @@ OCC_API int occnerf_mesh_texture_project(const int32_t *xy, const double *z, con
     using namespace occ;
     OCC_REQUIRE(h_K && h_E, "mesh_texture_project: null argument");
     OCC_REQUIRE(h_K[1] == 0.0, "mesh_texture_project: skew K[0,1] = %g is not built", h_K[1]);
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_texture_project: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
+    if (!tex_cell_ok("mesh_texture_project", n)) return 1;
     OCC_REQUIRE(H >= 1 && H <= kTexMaxSide && W >= 1 && W <= kTexMaxSide, "mesh_texture_project: H=%d W=%d outside 1..%d", H, W,
                 kTexMaxSide);
     OCC_REQUIRE(bias >= 0.0, "mesh_texture_project: bias=%g is negative or not a number", bias);
-    const int64_t P = (int64_t)n * (n - 1) / 2;
     OCC_REQUIRE(V >= 0 && V < (1ll << 31), "mesh_texture_project: V=%lld outside 0..2^31-1", (long long)V);
-    OCC_REQUIRE(T >= 0 && T < (1ll << 31) && T * P < (1ll << 31), "mesh_texture_project: T=%lld with %lld texels each reaches 2^31",
-                (long long)T, (long long)P);
+    int64_t P;
+    if (!tex_count_ok("mesh_texture_project", T, n, P)) return 1;
     if (T == 0) return 0;
     OCC_REQUIRE(xy && z && vflag && faces && keys && photo && inside && acc && seen && tri_w && status && ((verts && pflag) || V == 0),
                 "mesh_texture_project: null argument");
-    PhotoCamera cam;
-    cam.fx = h_K[0], cam.fy = h_K[4], cam.cx = h_K[2], cam.cy = h_K[5];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) cam.R[r * 3 + c] = h_E[r * 4 + c];
-        cam.t[r] = h_E[r * 4 + 3];
-    }
     hipLaunchKernelGGL(mesh_photo_weight_kernel, dim3((unsigned)((T + kTexThreads - 1) / kTexThreads)), dim3(kTexThreads), 0,
-                       as_stream(stream), verts, pflag, V, faces, T, cam, tri_w, status);
+                       as_stream(stream), verts, pflag, V, faces, T, screen_camera(h_K, h_E), tri_w, status);
     if (int rc = check_launch("mesh_texture_project (weights)")) return rc;
     const int64_t N = T * P;
     hipLaunchKernelGGL(mesh_texture_project_kernel, dim3((unsigned)((N + kTexThreads - 1) / kTexThreads)), dim3(kTexThreads), 0,
@@ -358,13 +286,10 @@ OCC_API int occnerf_mesh_texture_project(const int32_t *xy, const double *z, con
 OCC_API int occnerf_mesh_texture_blend(const int64_t *acc, const int32_t *seen, int64_t T, int32_t n, int32_t C, int32_t H,
                                        int32_t W, int32_t min_seen, uint8_t *atlas, uint8_t *seen_img, void *stream) {
     using namespace occ;
-    OCC_REQUIRE(n >= kTexMinCell && n <= kTexMaxCell, "mesh_texture_blend: n=%d outside %d..%d", n, kTexMinCell, kTexMaxCell);
+    if (!tex_cell_ok("mesh_texture_blend", n)) return 1;
     OCC_REQUIRE(min_seen >= 1, "mesh_texture_blend: min_seen=%d is not a whole number >= 1", min_seen);
-    const int64_t P = (int64_t)n * (n - 1) / 2;
-    OCC_REQUIRE(T >= 0 && T < (1ll << 31) && T * P < (1ll << 31), "mesh_texture_blend: T=%lld with %lld texels each reaches 2^31",
-                (long long)T, (long long)P);
-    OCC_REQUIRE(tex_layout_ok(T, n, C, H, W), "mesh_texture_blend: an atlas of H=%d W=%d with C=%d cells of %d per row does not hold "
-                "T=%lld triangles (W = C n, rows of cells * n <= H <= %d)", H, W, C, n, (long long)T, kTexMaxSide);
+    int64_t P;
+    if (!tex_count_ok("mesh_texture_blend", T, n, P) || !tex_atlas_ok("mesh_texture_blend", T, n, C, H, W)) return 1;
     if (T == 0) return 0;
     OCC_REQUIRE(acc && seen && atlas && seen_img, "mesh_texture_blend: null argument");
     const int64_t N = T * P;

@@ -1705,6 +1705,14 @@ def _mesh_raster_args(who, faces, xy, z, vflag, H, W):
     return pf, px, pz, pv, T, V, H, W
 
 
+def _mesh_keys(who, keys):
+    """mesh_raster's keys -> (address, H, W)."""
+    pk = _chk(keys, torch.int64, f'{who}: keys')
+    if keys.dim() != 2:
+        raise RuntimeError(f'{who}: keys must be int64 [H,W], got {tuple(keys.shape)}')
+    return pk, int(keys.shape[0]), int(keys.shape[1])
+
+
 def mesh_raster(faces, xy, z, vflag, H, W, faces_checked=False):
     """Triangles into the per-pixel keys (occnerf_mesh_raster): faces int32 [T,3] and mesh_project's xy / z / vflag on one
     device -> (keys int64 [H,W]: the bits of (float32 depth) << 32 | triangle index of the nearest covering triangle, -1 (all
@@ -1733,10 +1741,7 @@ def mesh_resolve(keys, counts, faces, xy, z, vflag, colors, bgcolor):
     """The image of mesh_raster's keys (occnerf_mesh_resolve): colors uint8 [V,3] on the device, bgcolor 3 values 0..255 on the
     host -> (cover uint8 [H,W], tri int32 [H,W] (-1 empty), depth float32 [H,W] (+inf empty), rgb uint8 [H,W,3]); counts[6]
     receives the covered pixels.  T = 0 or V = 0 launches nothing: the empty image."""
-    pk = _chk(keys, torch.int64, 'mesh_resolve: keys')
-    if keys.dim() != 2:
-        raise RuntimeError(f'mesh_resolve: keys must be int64 [H,W], got {tuple(keys.shape)}')
-    H, W = (int(s) for s in keys.shape)
+    pk, H, W = _mesh_keys('mesh_resolve', keys)
     pf, px, pz, pv, T, V, H, W = _mesh_raster_args('mesh_resolve', faces, xy, z, vflag, H, W)
     pn = _chk(counts, torch.int32, 'mesh_resolve: counts')
     if counts.numel() != len(MESH_RASTER_COUNTS) or counts.device != faces.device or keys.device != faces.device:
@@ -1789,19 +1794,32 @@ def mesh_texture_layout(T, n, who='mesh_texture'):
     return C, R, W, H, n * (n - 1) // 2
 
 
+def _mesh_texel_args(who, verts, faces, n):
+    """The mesh whose texels an entry walks: verts float32 [V,3], faces int32 [T,3] on its device, the cell edge n
+    -> (address of verts, of faces, n, V, T, P = n (n - 1) / 2, device)."""
+    n = _mesh_texture_cell(who, n)
+    pv = _mesh_points(f'{who}: verts', verts)
+    pf = _chk(faces, torch.int32, f'{who}: faces')
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
+        raise RuntimeError(f'{who}: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
+    V, T, P = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2
+    if V >= 1 << 31 or T * P >= 1 << 31:
+        raise RuntimeError(f'{who}: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
+    return pv, pf, n, V, T, P, verts.device
+
+
+def _mesh_face_status(who, status, V):
+    """One blocking read of a kernel's status word."""
+    if int(status.item()) != 0:
+        raise RuntimeError(f'{who}: a face index lies outside [0, {V})')
+
+
 def mesh_texel_points(verts, faces, n):
     """The canonical points of the atlas' texels (occnerf_mesh_texel_points): verts float32 [V,3], faces int32 [T,3], n the cell
     edge -> pts float32 [T,P,3], P = n (n - 1) / 2, on the device of verts.  A face index outside [0, V) is refused by name
     after one blocking read of the kernel's status word (the kernel itself never uses one as an address).  T = 0 launches
     nothing."""
-    n = _mesh_texture_cell('mesh_texel_points', n)
-    pv = _mesh_points('mesh_texel_points: verts', verts)
-    pf = _chk(faces, torch.int32, 'mesh_texel_points: faces')
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != verts.device:
-        raise RuntimeError(f'mesh_texel_points: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
-    V, T, P, dev = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2, verts.device
-    if V >= 1 << 31 or T * P >= 1 << 31:
-        raise RuntimeError(f'mesh_texel_points: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
+    pv, pf, n, V, T, P, dev = _mesh_texel_args('mesh_texel_points', verts, faces, n)
     pts = torch.empty(T, P, 3, device=dev, dtype=torch.float32)
     if T == 0:
         return pts
@@ -1809,8 +1827,7 @@ def mesh_texel_points(verts, faces, n):
     with _guard(verts):
         rc = _lib.lib().occnerf_mesh_texel_points(pv, V, pf, T, n, pts.data_ptr(), status.data_ptr(), _stream(verts))
     _lib.check(rc, 'mesh_texel_points')
-    if int(status.item()) != 0:
-        raise RuntimeError(f'mesh_texel_points: a face index lies outside [0, {V})')
+    _mesh_face_status('mesh_texel_points', status, V)
     return pts
 
 
@@ -1849,10 +1866,7 @@ def mesh_resolve_textured(keys, faces, xy, z, atlas, n, C, bgcolor):
     faces int32 [T,3], mesh_project's xy / z, atlas uint8 [aH,aW,3] of cell edge n with C cells per row, bgcolor 3 values
     0..255 on the host -> rgb uint8 [H,W,3].  The winner's four taps are its own texels.  No triangle: the background."""
     n = _mesh_texture_cell('mesh_resolve_textured', n)
-    pk = _chk(keys, torch.int64, 'mesh_resolve_textured: keys')
-    if keys.dim() != 2:
-        raise RuntimeError(f'mesh_resolve_textured: keys must be int64 [H,W], got {tuple(keys.shape)}')
-    H, W = (int(s) for s in keys.shape)
+    pk, H, W = _mesh_keys('mesh_resolve_textured', keys)
     pf, px, pz, _, T, V, H, W = _mesh_raster_args('mesh_resolve_textured', faces, xy, z, None, H, W)
     dev = faces.device
     if keys.device != dev:
@@ -1893,16 +1907,8 @@ def mesh_normal_bake(verts, vnormals, faces, tangents, creased, pts, n, C, atlas
     -> (atlas, offset float32 [T,P], flags uint8 [T,P], normal float32 [T,P,3]).  A face index outside [0, V) is refused by
     name after one blocking read of the kernel's status word (the kernel itself never uses one as an address).  T = 0 launches
     nothing."""
-    n = _mesh_texture_cell('mesh_normal_bake', n)
-    pv = _mesh_points('mesh_normal_bake: verts', verts)
+    pv, pf, n, V, T, P, dev = _mesh_texel_args('mesh_normal_bake', verts, faces, n)
     pn = _mesh_points('mesh_normal_bake: vnormals', vnormals)
-    pf = _chk(faces, torch.int32, 'mesh_normal_bake: faces')
-    dev = verts.device
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != dev:
-        raise RuntimeError(f'mesh_normal_bake: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
-    V, T, P = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2
-    if V >= 1 << 31 or T * P >= 1 << 31:
-        raise RuntimeError(f'mesh_normal_bake: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
     if tuple(vnormals.shape) != (V, 3) or vnormals.device != dev:
         raise RuntimeError(f'mesh_normal_bake: vnormals must be float32 [{V},3] on the device of verts, got {tuple(vnormals.shape)}')
     pt = _chk(tangents, torch.float32, 'mesh_normal_bake: tangents')
@@ -1933,8 +1939,7 @@ def mesh_normal_bake(verts, vnormals, faces, tangents, creased, pts, n, C, atlas
                                                  float(np.float32(level)), S, pa, offset.data_ptr(), flags.data_ptr(),
                                                  normal.data_ptr(), status.data_ptr(), _stream(verts))
     _lib.check(rc, 'mesh_normal_bake')
-    if int(status.item()) != 0:
-        raise RuntimeError(f'mesh_normal_bake: a face index lies outside [0, {V})')
+    _mesh_face_status('mesh_normal_bake', status, V)
     return atlas, offset, flags, normal
 
 
@@ -1952,10 +1957,7 @@ def mesh_resolve_lit(keys, faces, xy, z, vnormals, tangents, atlas, n, C, M, bgc
     -> (shade_geometry, shade_mapped) uint8 [H,W,3]: the interpolated vertex normal alone, and the normal the atlas gives in
     the frame a glTF viewer reconstructs.  No triangle: the background."""
     n = _mesh_texture_cell('mesh_resolve_lit', n)
-    pk = _chk(keys, torch.int64, 'mesh_resolve_lit: keys')
-    if keys.dim() != 2:
-        raise RuntimeError(f'mesh_resolve_lit: keys must be int64 [H,W], got {tuple(keys.shape)}')
-    H, W = (int(s) for s in keys.shape)
+    pk, H, W = _mesh_keys('mesh_resolve_lit', keys)
     pf, px, pz, _, T, V, H, W = _mesh_raster_args('mesh_resolve_lit', faces, xy, z, None, H, W)
     dev = faces.device
     if keys.device != dev:
@@ -1987,26 +1989,15 @@ def mesh_texture_project(xy, z, vflag, verts, pflag, faces, n, K, E, keys, photo
     -1 facing away.  A face index outside [0, V) is refused by name after one blocking read of the status word (no such index
     is used as an address).  T = 0 launches nothing."""
     who = 'mesh_texture_project'
-    n = _mesh_texture_cell(who, n)
-    pv = _mesh_points(f'{who}: verts', verts)
+    pv, pf, n, V, T, P, dev = _mesh_texel_args(who, verts, faces, n)
     pp = _chk(pflag, torch.uint8, f'{who}: pflag')
-    pf = _chk(faces, torch.int32, f'{who}: faces')
-    dev = verts.device
-    if faces.dim() != 2 or faces.shape[1] != 3 or faces.device != dev:
-        raise RuntimeError(f'{who}: faces must be int32 [T,3] on the device of verts, got {tuple(faces.shape)}')
-    V, T, P = int(verts.shape[0]), int(faces.shape[0]), n * (n - 1) // 2
-    if V >= 1 << 31 or T * P >= 1 << 31:
-        raise RuntimeError(f'{who}: V = {V} or T P = {T} x {P} reaches the limit of 2^31')
     N = T * P
     px, pz, pw = _chk(xy, torch.int32, f'{who}: xy'), _chk(z, torch.float64, f'{who}: z'), _chk(vflag, torch.uint8, f'{who}: vflag')
-    pk, ph, pi = _chk(keys, torch.int64, f'{who}: keys'), _chk(photo, torch.uint8, f'{who}: photo'), _chk(inside, torch.uint8, f'{who}: inside')
+    (pk, H, W), ph, pi = _mesh_keys(who, keys), _chk(photo, torch.uint8, f'{who}: photo'), _chk(inside, torch.uint8, f'{who}: inside')
     pa, ps = _chk(acc, torch.int64, f'{who}: acc'), _chk(seen, torch.int32, f'{who}: seen')
     if tuple(pflag.shape) != (V,) or tuple(xy.shape) != (N, 2) or tuple(z.shape) != (N,) or tuple(vflag.shape) != (N,):
         raise RuntimeError(f'{who}: pflag must be [{V}] and xy / z / vflag [{N},2] / [{N}] / [{N}], got {tuple(pflag.shape)}, '
                            f'{tuple(xy.shape)}, {tuple(z.shape)}, {tuple(vflag.shape)}')
-    if keys.dim() != 2:
-        raise RuntimeError(f'{who}: keys must be int64 [H,W], got {tuple(keys.shape)}')
-    H, W = (int(s) for s in keys.shape)
     if not (1 <= H <= MESH_RASTER_MAX_SIDE and 1 <= W <= MESH_RASTER_MAX_SIDE):
         raise RuntimeError(f'{who}: H = {H}, W = {W} outside 1..{MESH_RASTER_MAX_SIDE}')
     if tuple(photo.shape) != (H, W, 3) or tuple(inside.shape) != (H, W):
@@ -2031,8 +2022,7 @@ def mesh_texture_project(xy, z, vflag, verts, pflag, faces, n, K, E, keys, photo
                                                      E.ctypes.data_as(C.c_void_p), pk, ph, pi, H, W, bias, pa, ps,
                                                      tri_w.data_ptr(), status.data_ptr(), _stream(verts))
     _lib.check(rc, who)
-    if int(status.item()) != 0:
-        raise RuntimeError(f'{who}: a face index lies outside [0, {V})')
+    _mesh_face_status(who, status, V)
     return tri_w
 
 

@@ -361,10 +361,15 @@ def test_keys_refusals_and_wiring():
     for name in ('occnerf_mesh_texture_project', 'occnerf_mesh_texture_blend'):
         assert name in _lib.SIGNATURES and f'int {name}(' in header
     assert '#define OCCNERF_ABI_VERSION 5' in header and _lib.ABI_VERSION == 5
-    # the definition and the kernels state the same constants
-    src = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_texture.hip')).read()
-    for text, value in (('kPhotoNear = 1e-3', mrr.NEAR), ('kPhotoFar = 1048576.0', mrr.FAR), ('kPhotoGuard = 4194304.0', mrr.GUARD)):
-        assert text in src and float(text.split('= ')[1]) == float(value), text
+    # the definition and the kernels state the same constants: once, in the header the rasteriser and the weights share
+    csrc = os.path.join(ROOT, 'occnerf_amd', 'csrc')
+    src = open(os.path.join(csrc, 'mesh_screen.h')).read()
+    for text, value in (('kScreenNear = 1e-3', mrr.NEAR), ('kScreenFar = 1048576.0', mrr.FAR), ('kScreenGuard = 4194304.0', mrr.GUARD)):
+        assert src.count(text) == 1 and float(text.split('= ')[1]) == float(value), text
+    for name in ('mesh_raster.hip', 'mesh_texture.hip'):
+        own = re.sub(r'//[^\n]*', '', open(os.path.join(csrc, name)).read())
+        assert not re.search(r'\bk\w*(Near|Far|Guard)\w*\s*=', own), name
+        assert not re.search(r'1e-3|1048576|4194304|struct \w*Camera', own), name
 
 
 def test_write_glb_depends_on_the_png_only_through_its_bytes(tmp_path):

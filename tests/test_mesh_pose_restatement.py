@@ -248,9 +248,10 @@ def test_export_views_refuses_a_frame_through_the_shared_rule():
 
 
 def test_shared_mesh_header_keeps_the_kernels_rules():
-    """What mesh_raster.hip and mesh_texture.hip share lives in mesh_screen.h: it holds no fused multiply-add and no atomic of
-    its own, and every object file is rebuilt when it changes."""
+    """What mesh_raster.hip, mesh_texture.hip and mesh_normal.hip share lives in mesh_screen.h and mesh_atlas.h: neither holds a
+    fused multiply-add or an atomic of its own, and every object file is rebuilt when one changes."""
     make = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'Makefile')).read()
     rule = re.search(r'^build/%\.o:.*$', make, flags=re.M).group(0)
-    src = re.sub(r'//[^\n]*', '', open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_screen.h')).read()).lower()
-    assert 'fma' not in src and 'atomic' not in src and re.search(r'\bmesh_screen\.h\b', rule)
+    for header in ('mesh_screen.h', 'mesh_atlas.h'):
+        src = re.sub(r'//[^\n]*', '', open(os.path.join(ROOT, 'occnerf_amd', 'csrc', header)).read()).lower()
+        assert 'fma' not in src and 'atomic' not in src and re.search(rf'\b{re.escape(header)}\b', rule), header

@@ -299,9 +299,11 @@ def test_c_entries_refuse_bad_arguments_without_a_gpu():
     assert lib.occnerf_abi_version() == 5
     # the definition and the kernels state the same constants
     src = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_raster.hip')).read()
-    for text, value in (('kRasterWide = 64', rr.WIDE), ('kRasterNear = 1e-3', rr.NEAR), ('kRasterFar = 1048576.0', rr.FAR),
-                        ('kRasterGuard = 4194304.0', rr.GUARD), ('kRasterMaxSide = 16384', rr.MAX_SIDE)):
-        assert text in src and float(text.split('= ')[1]) == float(value), text
+    screen = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'mesh_screen.h')).read()          # the vertex rule's limits live there
+    for text, value, where in (('kRasterWide = 64', rr.WIDE, src), ('kScreenNear = 1e-3', rr.NEAR, screen),
+                               ('kScreenFar = 1048576.0', rr.FAR, screen), ('kScreenGuard = 4194304.0', rr.GUARD, screen),
+                               ('kRasterMaxSide = 16384', rr.MAX_SIDE, src)):
+        assert text in where and float(text.split('= ')[1]) == float(value), text
     assert 'fma' not in re.sub(r'//[^\n]*', '', src).lower()
     make = open(os.path.join(ROOT, 'occnerf_amd', 'csrc', 'Makefile')).read()
     assert re.search(r'^SRCS\s*:=.*\bmesh_raster\.hip\b', make, flags=re.M)

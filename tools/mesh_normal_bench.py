@@ -18,6 +18,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             and its four outputs against the device's as bit patterns;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import importlib.util
 import json
 import os
@@ -132,7 +133,11 @@ def cmd_device(a):
                      'tangents_host_ms': round(host_ms, 1), 'bake_normal_map_wall_ms': _stats(whole),
                      'bake_normal_map_seconds': stats['seconds'],
                      'view': [VIEW, VIEW], 'view_pixels_covered': int(cover.sum().item()),
-                     'lit_mean_abs_diff': float(diff.double().mean().item()) if diff.numel() else None}
+                     'lit_mean_abs_diff': float(diff.double().mean().item()) if diff.numel() else None,
+                     # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                     'sha256': {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                                for k, t in (('atlas', atlas), ('offset', offset), ('flags', flags), ('normal', normal),
+                                             ('shade_geometry', lit[0]), ('shade_mapped', lit[1]))}}
         Ts = min(SUBSET, T)
         fs = faces[:Ts].contiguous()
         Cs, _, Ws, Hs, _ = mesh.atlas_layout(Ts, n)

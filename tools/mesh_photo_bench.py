@@ -20,6 +20,7 @@ Steps (each a sub-command, so the shell script can bound each one):
             against the device's;
   merge     the partial results as one JSON object."""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -137,6 +138,10 @@ def cmd_device(a):
                      'owned_texels': N, 'frame': [VIEW, VIEW], 'bias_m': h,
                      'texels_seen_in_the_frame': n_seen, 'triangles_facing_away': int((tri_w < 0).sum().item()),
                      'triangles_weighted': int((tri_w > 0).sum().item()),
+                     # the whole outputs, for holding two builds of the library against each other (OCCNERF_HIP_LIB)
+                     'sha256': {k: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+                                for k, t in (('texel_points', q), ('xy', xy), ('z', z), ('vflag', vflag), ('keys', keys), ('tri_w', tri_w),
+                                             ('acc', acc), ('seen', seen), ('photo_atlas', out[0]), ('seen_img', out[1]))},
                      'bytes': {'texel_points': {'read': V * 12 + T * 12, 'written': N * 12},
                                'project_texels': {'read': N * 12, 'written': N * 17},
                                'project_vertices': {'read': V * 12, 'written': V * 17},
